@@ -2,7 +2,19 @@
 """Benchmark of the MI355X pairwise kmer-distance hot path (driver contract).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c2r|c3|c4|c5]
-                    [--rows A:B] [--force-exchange]
+                    [--rows A:B] [--force-exchange] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs if
+--dump-outputs is given and prints the result line (metric, value,
+ms_per_step, the workload and the setup times). --full goes on after the
+timed steps with everything else: each kernel family timed alone and the
+roofline built from it, the sample recount against poisoned outputs
+(`verified`; a mismatch exits 1), the end-to-end figure and the CPU
+baselines (--no-cpu-baseline leaves those out), and adds them to the line.
+--dump-outputs DIR writes what the last timed step computed, this rank's
+rows of I and D, as DIR/I.npy and DIR/D.npy (float64; see dump_outputs):
+the inputs are generated from fixed seeds, so two builds can be compared
+array for array.
 
 Metric (BASELINE.json): genome-pair distances/sec over the N×N upper
 triangle (unordered pairs i<j). Default workload = configs[1] (C2):
@@ -121,7 +133,13 @@ def main():
     ap.add_argument("--length", type=int, default=0, help="override genome length (testing)")
     ap.add_argument("--method", default="", choices=["", "auto", "bitset", "sorted"],
                     help="override the config's kernel family (experiments; the config's own is the bench line)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: per-kernel "
+                         "timings and the roofline, the sample recount against poisoned outputs, the "
+                         "end-to-end figure and the CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (this rank's rows of I and D) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--pageable", action="store_true",
                     help="hand the pack the generated bytes in pageable memory instead of a gdist_host_alloc "
                          "buffer (the runtime's staged copies, ~6 GB/s)")
@@ -141,6 +159,8 @@ def main():
                     help="per-launch HBM traffic measured by rocprofv3 PMC passes "
                          "(default: the profiles/pmc_<config>*.json taken on the line's kernel, if any)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -361,6 +381,56 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed_max = max_over_ranks(elapsed)
+    pairs_all = N * (N - 1) // 2
+    pairs_job = pairs_rank if slice_rows else pairs_all      # a slice's pairs are all this job computes
+    value = pairs_job * args.steps / elapsed_max
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, dI, dD, N, r0, r1, rank, world)
+    config = {"workload": f"{args.config}: {cfg['desc']}", "genomes": N, "genome_length": cfg["length"],
+              "k": cfg["k"], "pairs_per_step": pairs_job, "parallelism": f"rows{world}",
+              "slice_rows": slice_rows, "exchange": xplan,
+              "bitset_words_per_set": width_words or None,
+              "dictionary_size": (dict_size if method == "bitset" else None),
+              "method": method, "auto": auto, "rare_tier": rare, "complement_sparse": sparse_words,
+              "variant_tier": variant,
+              "options": options or None}
+    setup = {"generate": round(gen_s, 2), "host_free": round(free_s, 3), "pack": round(pack_s, 2),
+             "represent": round(represent_s, 2), "total": round(setup_s, 2),
+             "build": ({k: (round(v, 1) if isinstance(v, float) else v) for k, v in build_t.items()}
+                       if build_t else None)}
+
+    def teardown():
+        if dist:
+            dist.barrier()
+            ctx.comm_destroy()
+            dist.destroy_process_group()
+        elif exchange:
+            ctx.comm_destroy()
+
+    if not args.full:
+        # the plain run ends here: the headline figure, nothing measured beside it
+        if rank == 0:
+            print(json.dumps({
+                "metric": "genome-pair distances/sec (N×N)",
+                "value": round(value, 1),
+                "unit": "pairs/s",
+                "n_gpus": world,
+                "steps": args.steps,
+                "warmup": args.warmup,
+                "ms_per_step": round(elapsed_max / args.steps * 1e3, 4),
+                "higher_is_better": True,
+                "scaling": "weak",
+                "vs_baseline": None,
+                "dtype": "u64" if method != "sketch" else "i32",
+                "data": "synthetic (splitmix64 genomes, SURVEY 8d)",
+                "config": config,
+                "setup_s": setup,
+                "dumped": dumped,
+                "full": False,
+            }), flush=True)
+        teardown()
+        return
     # Kernel times, after the timed region: replayed steps record no timing
     # events by default (they cost 13-18 us a step), so a short loop with
     # option step_timing = 1 reads the steps' HIP-event spans (on the
@@ -395,9 +465,6 @@ def main():
         ctx.set_option("serial_step", prev_serial)
         fam_ms = {f: float(np.mean(v)) for f, v in acc.items() if v}
     sparse_k_ms = fam_ms.get("sparse")
-    pairs_all = N * (N - 1) // 2
-    pairs_job = pairs_rank if slice_rows else pairs_all      # a slice's pairs are all this job computes
-    value = pairs_job * args.steps / elapsed_max
     k_avg_ms = float(np.mean(kernel_ms)) if kernel_ms else 0.0
     # end to end: the whole job for one pass over the collection = pack +
     # represent (dictionary, bitsets / sketches) + one step, max over ranks
@@ -684,22 +751,12 @@ def main():
             "vs_baseline": None,
             "dtype": "u64" if method != "sketch" else "i32",
             "data": "synthetic (splitmix64 genomes, SURVEY 8d)",
-            "config": {"workload": f"{args.config}: {cfg['desc']}", "genomes": N, "genome_length": cfg["length"],
-                       "k": cfg["k"], "pairs_per_step": pairs_job, "parallelism": f"rows{world}",
-                       "slice_rows": slice_rows, "exchange": xplan,
-                       "bitset_words_per_set": width_words or None,
-                       "dictionary_size": (dict_size if method == "bitset" else None),
-                       "method": method, "auto": auto, "rare_tier": rare, "complement_sparse": sparse_words,
-                       "variant_tier": variant,
-                       "options": options or None},
+            "config": config,
             "roofline": with_readings(roof),
             "verified": verified,
             "cpu_baseline": cpu,
             "cpu_optimized": cpu_opt,
-            "setup_s": {"generate": round(gen_s, 2), "host_free": round(free_s, 3), "pack": round(pack_s, 2), "represent": round(represent_s, 2),
-                        "total": round(setup_s, 2),
-                        "build": ({k: (round(v, 1) if isinstance(v, float) else v) for k, v in build_t.items()}
-                                  if build_t else None)},
+            "setup_s": setup,
             "end_to_end": {"pairs_per_s": round(pairs_job / e2e_s, 1), "seconds": round(e2e_s, 3),
                            "first_call_s": round(first_call_s, 4) if first_call_s is not None else None,
                            "plan_s": (round(first_call_s - elapsed_max / args.steps, 4)
@@ -711,17 +768,58 @@ def main():
                                    "runs; plan_s = that call minus a steady step); synthetic-genome "
                                    "generation and the release of the caller's host buffer (setup_s.host_free) "
                                    "excluded; max over ranks"},
+            "dumped": dumped,
+            "full": True,
         }
         print(json.dumps(out), flush=True)
     if verified is not None and not verified["ok"]:
         log(f"rank {rank}: device output disagrees with the independent recount")
         sys.exit(1)
-    if dist:
-        dist.barrier()
-        ctx.comm_destroy()
-        dist.destroy_process_group()
-    elif exchange:
-        ctx.comm_destroy()
+    teardown()
+
+
+DUMP_BYTES = 64 << 20                # --dump-outputs writes at most this much, all ranks together
+DUMP_SEED = 0
+
+
+def dump_outputs(outdir, dI, dD, N, r0, r1, rank=0, world=1):
+    """Write this rank's block of the step's outputs, read back from the
+    device buffers the timed steps wrote: I (|A∩B|, or the sketches' common
+    count) and D (the fp64 distance), both as float64 (the counts are exact
+    in it), to outdir/I.npy and outdir/D.npy (I_rank<r>.npy, D_rank<r>.npy
+    when there are several ranks). The step computes the upper triangle and
+    leaves entries with column <= row untouched (include/gdist.h), so they
+    are written as 0. A block past the byte limit is cut to a fixed sample
+    of its rows (and, past one row, of its columns) drawn from DUMP_SEED:
+    the same arguments give the same sample."""
+    rows = r1 - r0
+    budget = DUMP_BYTES // world // 16            # elements of each array: 8 B in I + 8 B in D
+    ncol = min(N, max(1, budget))
+    nrow = min(rows, max(1, budget // ncol))
+    rng = np.random.default_rng(DUMP_SEED)
+    pick_r = np.arange(rows) if nrow == rows else np.sort(rng.choice(rows, nrow, replace=False))
+    pick_c = np.arange(N) if ncol == N else np.sort(rng.choice(N, ncol, replace=False))
+    if nrow == rows and rows > 0:
+        I = dI.to_host(np.int32, rows * N).reshape(rows, N)
+        D = dD.to_host(np.float64, rows * N).reshape(rows, N)
+    else:
+        I = np.zeros((nrow, N), np.int32)
+        D = np.zeros((nrow, N), np.float64)
+        for t, r in enumerate(pick_r):
+            I[t] = dI.to_host(np.int32, N, int(r) * N)
+            D[t] = dD.to_host(np.float64, N, int(r) * N)
+    untouched = np.arange(N)[None, :] <= (r0 + pick_r)[:, None]
+    I = np.where(untouched, 0, I)[:, pick_c].astype(np.float64)
+    D = np.where(untouched, 0.0, D)[:, pick_c]
+    os.makedirs(outdir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    names = []
+    for name, a in (("I", I), ("D", D)):
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), np.ascontiguousarray(a))
+        names.append(f"{name}{suffix}.npy")
+    return {"dir": outdir, "arrays": names, "dtype": "float64", "rows": int(nrow), "of_rows": int(rows),
+            "cols": int(ncol), "of_cols": int(N), "seed": DUMP_SEED,
+            "what": "the last timed step's I and D of this rank's rows; entries with column <= row hold 0"}
 
 
 def _kmer_codes(seq: bytes, k: int, protein: bool) -> np.ndarray:

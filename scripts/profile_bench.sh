@@ -6,7 +6,7 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
-ARGS=${BENCH_ARGS:-"--steps 5 --warmup 1 --no-cpu-baseline"}
+ARGS=${BENCH_ARGS:-"--steps 5 --warmup 1 --full --no-cpu-baseline"}
 OUT=gpurun_out
 mkdir -p $OUT
 timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_trace -o run -- \

@@ -6,7 +6,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 CFG=$1; N=$2; KERN=$3; OUT=$4; EXTRA=${5:-}
-ARGS="--config $CFG --steps 20 --warmup 3 --no-cpu-baseline $EXTRA"
+ARGS="--config $CFG --steps 20 --warmup 3 --full --no-cpu-baseline $EXTRA"
 mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_trace -o run -- \
     python3 bench.py $ARGS > $OUT/prof_trace.json 2> $OUT/prof_trace.err &&

@@ -1,28 +1,31 @@
 """CPU: every `Name.java:N[-M]` citation in the product, oracle and host code
 resolves against the reference sources (the file exists, every cited line is
 inside it), and where a cited line carries a message or output literal, the
-literal is on the cited lines. Skips when /root/reference is absent (the GPU
-box never has it)."""
-import glob
+literal is on the cited lines.
+
+The reference sources are not part of this repository, so the tests read an
+index of them, tests/golden/reference_index.json: the line count of every
+reference file, and one hash for every (file, cited lines, literal) that was
+found on its cited lines when the index was made. A citation moved to
+another line, or a new one, is not in the index and fails until
+tests/golden/make_reference_index.py is run against the reference sources
+again (it refuses a literal that is not on the lines cited for it)."""
+import hashlib
+import json
 import os
 import re
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src/main/java"
+INDEX = os.path.join(ROOT, "tests", "golden", "reference_index.json")
 SCANNED = ["include", "oracle", "genome.distance_amd/gdist", "genome.distance_amd/csrc", "tests",
            "INTEGRATION.md", "DESIGN.md", "bench.py", "__graft_entry__.py"]
 CITE = re.compile(r"([A-Za-z]+\.java):(\d+(?:-\d+)?(?:,\s?\d+(?:-\d+)?)*)")
 LITERAL = re.compile(r'"((?:[^"\\]|\\.){12,})"')
 
 
-def _ref_files():
-    out = {}
-    for p in glob.glob(os.path.join(REF, "**", "*.java"), recursive=True):
-        with open(p, errors="replace") as f:
-            out[os.path.basename(p)] = f.read().split("\n")
-    return out
+def _index():
+    with open(INDEX) as f:
+        return json.load(f)
 
 
 def _sources():
@@ -51,17 +54,37 @@ def _citations():
                     yield path, ln, line, m.group(1), list(_ranges(m.group(2)))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference sources absent")
+def _cited_literals():
+    """(path, line number, reference file, cited ranges, literal, probe) of
+    every host-code line that raises a reference message or writes a
+    reference header and cites the reference line it follows; the probe is
+    the part of the literal that must stand on the cited lines."""
+    for path, ln, line, name, ranges in _citations():
+        if not path.endswith(".py") or not ("raise " in line or ".write(" in line):
+            continue
+        for lit in LITERAL.findall(line):
+            if lit.startswith(("{", "%")):
+                continue
+            probe = lit.split("{")[0].replace("\\n", "")[:40]
+            if len(probe) >= 8:
+                yield path, ln, name, ranges, lit, probe
+
+
+def literal_key(name, ranges, probe):
+    spec = ",".join(f"{a}-{b}" for a, b in ranges)
+    return hashlib.sha256(f"{name}:{spec}:{probe}".encode()).hexdigest()[:20]
+
+
 def test_citations_resolve():
-    ref = _ref_files()
+    lines = _index()["lines"]
     bad, n = [], 0
     for path, ln, _, name, ranges in _citations():
         n += 1
         rel = os.path.relpath(path, ROOT)
-        if name not in ref:
+        if name not in lines:
             bad.append(f"{rel}:{ln}: {name} is not a reference file")
             continue
-        nlines = len(ref[name])
+        nlines = lines[name]
         for a, b in ranges:
             if not (1 <= a <= b <= nlines):
                 bad.append(f"{rel}:{ln}: {name}:{a}-{b} outside its {nlines} lines")
@@ -69,26 +92,18 @@ def test_citations_resolve():
     assert not bad, "\n".join(bad)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference sources absent")
 def test_cited_literals_are_on_the_cited_lines():
     """A host-code line that raises a reference message or writes a reference
     header, and cites the reference line it follows, must cite the line that
     holds that text (catches citations shifted to a wrong but existing line)."""
-    ref = _ref_files()
+    idx = _index()
+    found = set(idx["literals_on_cited_lines"])
     bad, checked = [], 0
-    for path, ln, line, name, ranges in _citations():
-        if not path.endswith(".py") or name not in ref or not ("raise " in line or ".write(" in line):
+    for path, ln, name, ranges, lit, probe in _cited_literals():
+        if name not in idx["lines"]:
             continue
-        lits = [x for x in LITERAL.findall(line) if not x.startswith(("{", "%"))]
-        if not lits:
-            continue
-        text = "\n".join("\n".join(ref[name][a - 1:b]) for a, b in ranges)
-        for lit in lits:
-            probe = lit.split("{")[0].replace("\\n", "")[:40]
-            if len(probe) < 8:
-                continue
-            checked += 1
-            if probe not in text:
-                bad.append(f"{os.path.relpath(path, ROOT)}:{ln}: {lit!r} not on {name}:{ranges}")
+        checked += 1
+        if literal_key(name, ranges, probe) not in found:
+            bad.append(f"{os.path.relpath(path, ROOT)}:{ln}: {lit!r} not on {name}:{ranges}")
     assert checked >= 8, f"only {checked} cited literals found"
     assert not bad, "\n".join(bad)
