@@ -1396,6 +1396,57 @@ int gdist_lsh_closest(gdist_ctx* ctx, const gdist_lsh* lsh, const gdist_sets* qu
     });
 }
 
+// ---------------------------------------------------------------------------
+int gdist_closest(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
+                  unsigned flags, int n, double max_dist, int64_t* idx_out, double* d_out, int32_t* count_out) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_sets(sets);
+        GD_REQUIRE(sets->ctx == ctx, "sets belong to another context");
+        GD_REQUIRE(0 <= r0 && r0 <= r1 && r1 <= sets->nsets && 0 <= c0 && c0 <= c1 && c1 <= sets->nsets,
+                   "row/column range outside the set collection");
+        GD_REQUIRE(n >= 0 && n <= GDIST_CLOSEST_MAX_N, "n outside 0 .. GDIST_CLOSEST_MAX_N");
+        GD_REQUIRE(max_dist == max_dist, "max_dist is NaN");
+        GD_REQUIRE(!(flags & (GDIST_UPPER_TRIANGLE | GDIST_OUT_DEVICE)),
+                   "gdist_closest supports neither GDIST_UPPER_TRIANGLE nor GDIST_OUT_DEVICE");
+        const bool sketch = sets->kind == GDIST_SKETCH;
+        if (sketch) {
+            check_codes(sets);
+        } else {
+            GD_REQUIRE(method >= GDIST_METHOD_AUTO && method <= GDIST_METHOD_BITSET, "unknown method");
+            GD_REQUIRE(method != GDIST_METHOD_SORTED || sets->has_codes, "this collection holds bitsets only");
+        }
+        GD_REQUIRE(sets->nsets < (int64_t)UINT32_MAX, "too many sets for 32-bit column keys");
+        const int64_t nr = r1 - r0, nc = c1 - c0;
+        GD_REQUIRE(nr == 0 || (count_out && (n == 0 || (idx_out && d_out))), "null output");
+        ctx->closest_matrix_ms = ctx->closest_select_ms = -1.0;
+        if (nr == 0) return;
+        if (n == 0 || nc == 0) {
+            std::fill(count_out, count_out + nr, 0);
+            if (n) {
+                std::fill(idx_out, idx_out + nr * n, (int64_t)-1);
+                std::fill(d_out, d_out + nr * n, 1.0);
+            }
+            return;
+        }
+        auto* s = const_cast<gdist_sets*>(sets);
+        const int m = sketch ? GDIST_METHOD_AUTO : resolve_method(ctx, s, method, (double)nr * (double)nc);
+        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
+        ctx->last = Timing{};
+        gdist::closest(ctx, s, r0, r1, c0, c1, m, flags, n, max_dist, idx_out, d_out, count_out);
+    });
+}
+
+int gdist_ctx_closest_timing(gdist_ctx* ctx, double* matrix_ms, double* select_ms) {
+    return guard([&] {
+        GD_REQUIRE(ctx != nullptr, "null context");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        if (matrix_ms) *matrix_ms = ctx->closest_matrix_ms;
+        if (select_ms) *select_ms = ctx->closest_select_ms;
+    });
+}
+
 int gdist_comm_unique_id(char id[GDIST_UNIQUE_ID_BYTES]) {
     return guard([&] {
         static_assert(sizeof(ncclUniqueId) <= GDIST_UNIQUE_ID_BYTES, "unique id size");

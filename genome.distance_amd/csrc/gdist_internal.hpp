@@ -258,7 +258,9 @@ struct Timing {
     X(DENSE_FIRST, "dense_first")             /* the dense tiles issued before the side stream's launches (default: without sparse words) */ \
     X(REPS_SPLIT, "reps_split")               /* greedy reps of a gathered collection: 1 (default) columns sharded over the ranks, 0 every rank all */ \
     X(SERIAL_STEP, "serial_step")             /* 1: the side stream's kernel families on the main stream, in turn (timing) */ \
-    X(SPLIT_BUILD, "split_build")             /* gathered collection on R ranks: each builds 1/R and all-gathers (default); 0 every rank all; k >= 2 without peers: k shares in turn here */
+    X(SPLIT_BUILD, "split_build")             /* gathered collection on R ranks: each builds 1/R and all-gathers (default); 0 every rank all; k >= 2 without peers: k shares in turn here */ \
+    X(CLOSEST_ROWS, "closest_rows")           /* gdist_closest: query rows a block (default: by memory) */ \
+    X(CLOSEST_COLS, "closest_cols")           /* gdist_closest: columns a chunk (default: by memory) */
 
 enum Opt : int {
 #define GDIST_OPT_ENUM(id, name) OPT_##id,
@@ -328,6 +330,9 @@ struct gdist_ctx {
     int64_t ring_n = 0;                      // calls whose kernel events were recorded
     bool pending = false;                    // the last call's times are not read yet
     bool last_kernel = false;
+    // the last gdist_closest call made with option time_kernels = 1: its
+    // matrix kernels and its select kernel, ms over all steps (-1: not timed)
+    double closest_matrix_ms = -1.0, closest_select_ms = -1.0;
     gdist_ctx() { for (auto& o : opt) o = gdist::kOptUnset; }
     int64_t option(gdist::Opt o, int64_t dflt) const { return opt[o] == gdist::kOptUnset ? dflt : opt[o]; }
     bool has_option(gdist::Opt o) const { return opt[o] != gdist::kOptUnset; }
@@ -687,6 +692,11 @@ void zero_counts(gdist_ctx* ctx, int64_t r0, int64_t r1, int64_t c0, int64_t c1,
 void distance_epilogue(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, int64_t c0,
                        int64_t c1, bool upper, unsigned flags, const int32_t* d_I, int64_t ldI,
                        double* d_D, int64_t ldD);
+
+// closest.hip — exact top-n within max_dist per query row (gdist_closest)
+void closest_blocks(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem, int64_t* rows, int64_t* cols);
+void closest(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
+             unsigned flags, int n, double max_dist, int64_t* idx_out, double* d_out, int32_t* count_out);
 
 // lsh.hip
 void lsh_build(gdist_ctx* ctx, const gdist_sets* sk, int stages, int buckets, uint64_t seed, gdist_lsh* L);

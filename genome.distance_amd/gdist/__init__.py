@@ -5,7 +5,8 @@ Python host mirror of the reference API over the C-ABI library libgdist.so
 loudly if it is missing: there is no CPU fallback on the product path.
 """
 from . import _lib
-from ._lib import (AMBIG_DEFAULT, AMBIG_KEEP, AMBIG_SKIP, BITSET_KEEP_SINGLETONS, EMPTY_NAN, METHOD_AUTO,
+from ._lib import (AMBIG_DEFAULT, AMBIG_KEEP, AMBIG_SKIP, BITSET_KEEP_SINGLETONS, CLOSEST_KEEP_SELF, CLOSEST_MAX_N,
+                   EMPTY_NAN, METHOD_AUTO,
                    METHOD_BITSET, METHOD_SORTED, NO_CASE_FOLD, QUERY_ALL, QUERY_ANY_LE, QUERY_ARGMIN,
                    SKETCH_JACCARD, STRAND_BOTH, STRAND_CANON, STRAND_FWD, UPPER_TRIANGLE, GdistError)
 from .fasta import Sequence, read_fasta, write_fasta

@@ -23,6 +23,7 @@ METHOD_AUTO, METHOD_SORTED, METHOD_BITSET = 0, 1, 2
 BITSET_KEEP_SINGLETONS = 0x1
 ALLGATHER_CONSUME = 0x1
 QUERY_ALL, QUERY_ANY_LE, QUERY_ARGMIN = 0, 1, 2
+CLOSEST_KEEP_SELF, CLOSEST_MAX_N = 0x1000, 512
 UNIQUE_ID_BYTES = 128
 OPTION_DEFAULT = -(1 << 63)   # GDIST_OPTION_DEFAULT
 
@@ -133,6 +134,9 @@ _SIGS = {
     "gdist_lsh_build": (C.c_int, [_ctxp, _setp, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]),
     "gdist_lsh_free": (C.c_int, [C.c_void_p]),
     "gdist_lsh_closest": (C.c_int, [_ctxp, C.c_void_p, _setp, C.c_int, _dbl, _i64p, _dblp, _i32p]),
+    "gdist_closest": (C.c_int, [_ctxp, _setp, _i64, _i64, _i64, _i64, C.c_int, _u32, C.c_int, _dbl, _i64p, _dblp,
+                                _i32p]),
+    "gdist_ctx_closest_timing": (C.c_int, [_ctxp, _dblp, _dblp]),
     "gdist_comm_unique_id": (C.c_int, [C.c_char_p]),
     "gdist_comm_init": (C.c_int, [_ctxp, C.c_char_p, C.c_int, C.c_int]),
     "gdist_comm_init_host": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_void_p, _vp]),

@@ -119,6 +119,13 @@ class Context:
         L.check(L.lib.gdist_ctx_kernel_ms(self.h, self.KERNEL_FAMILIES[family], C.byref(v)))
         return v.value
 
+    def closest_timing(self) -> tuple[float, float]:
+        """(matrix kernels ms, select kernel ms) of the last closest() call made
+        with option time_kernels = 1, summed over its steps (-1: not timed)."""
+        m, s = C.c_double(), C.c_double()
+        L.check(L.lib.gdist_ctx_closest_timing(self.h, C.byref(m), C.byref(s)))
+        return m.value, s.value
+
     def recent_timings(self, n: int) -> list[float]:
         """Kernel ms of the last n matrix calls, oldest first (waits for them)."""
         out = np.zeros(max(n, 1), dtype=np.float64)
@@ -291,6 +298,32 @@ class _Handle:
 
     def __len__(self) -> int:
         return self.info()[2]
+
+    def _closest(self, n: int, max_dist: float, rows, cols, method: int, flags: int, keep_self: bool):
+        """gdist_closest over rows x cols: (idx[nr, n] int64, d[nr, n] float64, count[nr] int32)."""
+        ns = len(self)
+        r0, r1 = rows or (0, ns)
+        c0, c1 = cols or (0, ns)
+        nr = max(r1 - r0, 0)
+        idx = np.full((nr, max(n, 0)), -1, dtype=np.int64)
+        d = np.ones((nr, max(n, 0)), dtype=np.float64)
+        cnt = np.zeros(nr, dtype=np.int32)
+        # non-empty buffers behind empty results: the library is never handed a null output
+        bi = idx if idx.size else np.zeros(1, dtype=np.int64)
+        bd = d if d.size else np.zeros(1, dtype=np.float64)
+        bc = cnt if cnt.size else np.zeros(1, dtype=np.int32)
+        fl = flags | (L.CLOSEST_KEEP_SELF if keep_self else 0)
+        L.check(L.lib.gdist_closest(self.ctx.h, self.h, r0, r1, c0, c1, method, fl, int(n), float(max_dist),
+                                    L.ptr(bi, C.c_int64), L.ptr(bd, C.c_double), L.ptr(bc, C.c_int32)))
+        return idx, d, cnt
+
+    def getClosest(self, n: int, max_dist: float, **kw) -> list[list[tuple[int, float]]]:
+        """getClosest(kmers, n, maxDist) for every row of closest(n, max_dist, **kw)
+        (MashProcessor.java:150, FindProcessor.java:110), exhaustively: per query
+        [(set, distance)] nearest first (ties by index), at most n, distance <=
+        max_dist — the shape of LSHIndex.getClosest."""
+        idx, d, cnt = self.closest(n, max_dist, **kw)
+        return [[(int(idx[q, r]), float(d[q, r])) for r in range(cnt[q])] for q in range(len(cnt))]
 
     def allgather(self, consume: bool = False):
         """Concatenation of every rank's local collection, in rank order
@@ -564,6 +597,16 @@ class KmerSets(_Handle):
         L.check(L.lib.gdist_intersect_matrix(self.ctx.h, self.h, rows[0], rows[1], cols[0], cols[1], method,
                                              fl, d_I, d_D, ld))
 
+    def closest(self, n: int, max_dist: float, rows: tuple[int, int] | None = None,
+                cols: tuple[int, int] | None = None, method: int = L.METHOD_AUTO, flags: int = 0,
+                keep_self: bool = False):
+        """Exact nearest neighbours (gdist_closest): for every set of `rows` the n
+        sets of `cols` with the smallest Jaccard distance <= max_dist, ordered by
+        (distance, index), the set itself left out unless keep_self. Returns
+        (idx[nr, n] int64, d[nr, n] float64, count[nr] int32); unused slots are
+        -1 / 1.0. d is bit-identical to matrix()'s D; the N x N stays on the device."""
+        return self._closest(n, max_dist, rows, cols, method, flags, keep_self)
+
     def row_query(self, q: int, cols: Iterable[int], mode: int = L.QUERY_ALL, t: float = 1.0):
         cl = np.ascontiguousarray(np.fromiter(cols, dtype=np.int64))
         D = np.zeros(max(len(cl), 1), dtype=np.float64)
@@ -660,6 +703,13 @@ class SketchSets(_Handle):
         L.check(L.lib.gdist_sketch_matrix(self.ctx.h, self.h, r0, r1, c0, c1, fl, common.ctypes.data,
                                           D.ctypes.data, max(nc, 1)))
         return common, D
+
+    def closest(self, n: int, max_dist: float, rows: tuple[int, int] | None = None,
+                cols: tuple[int, int] | None = None, flags: int = 0, keep_self: bool = False):
+        """Exact nearest neighbours by sketch distance (gdist_closest; flags:
+        SKETCH_JACCARD, EMPTY_NAN): the same result shape as KmerSets.closest, d
+        bit-identical to matrix()'s D."""
+        return self._closest(n, max_dist, rows, cols, L.METHOD_AUTO, flags, keep_self)
 
     def matrix_device(self, d_common: int | None, d_D: int | None, ld: int, rows, cols, upper=False, flags=0):
         fl = flags | L.OUT_DEVICE | (L.UPPER_TRIANGLE if upper else 0)

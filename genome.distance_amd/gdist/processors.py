@@ -328,3 +328,40 @@ def width_processor(rows: Iterable[tuple[str, str]], min_size: int, max_size: in
     if prots:
         flush(group_id, prots)
     return target
+
+
+def closest_genomes(queries: Sequence[Genome], subjects: Sequence[Genome], out: TextIO, kmer_size: int = 21,
+                    neighbors: int = 10, max_dist: float = 0.9, flags: int = 0,
+                    ctx: Context | None = None) -> tuple[int, int, int]:
+    """The `mash` table answered exactly: for every query genome its `neighbors`
+    closest subject genomes within `max_dist` by kmer (Jaccard) distance, over
+    every subject instead of the LSH buckets of MashProcessor.java:150 (defaults
+    MashProcessor.java:104-106). Subjects and queries are packed as one
+    collection and one KmerSets.closest call takes the queries as rows and the
+    subjects as columns. The header is MashProcessor.java:144 and each row
+    MashProcessor.java:161; as the reference does, a row prints the SUBJECT id
+    and name first, then the query's, under a header that names the query
+    first. Rows of one query are nearest first (ties by subject order). Returns
+    (queries, neighbours found, searches with none), the counters of
+    MashProcessor.java:168."""
+    # the header of MashProcessor.java:144
+    out.write("query_id\tquery_name\tsubject_id\tsubject_name\tdistance\n")
+    nq, ns = len(queries), len(subjects)
+    if nq == 0:
+        return 0, 0, 0
+    if ns == 0:
+        return nq, 0, nq
+    allg = list(subjects) + list(queries)
+    sets = KmerSets.from_sequences([g.kmer_text() for g in allg], kmer_size, KmerType.DNA, flags, ctx)
+    idx, d, cnt = sets.closest(neighbors, max_dist, rows=(ns, ns + nq), cols=(0, ns))
+    found = none = 0
+    for a, q in enumerate(queries):
+        if cnt[a] == 0:
+            none += 1
+            continue
+        for r in range(cnt[a]):
+            s = subjects[int(idx[a, r])]
+            # "%s\t%s\t%s\t%s\t%8.3f%n" of MashProcessor.java:161: subject first
+            out.write(f"{s.id}\t{s.name}\t{q.id}\t{q.name}\t{java_format_f(float(d[a, r]), 8, 3)}\n")
+            found += 1
+    return nq, found, none

@@ -24,6 +24,9 @@
  *                          sequential early exit                 FastaDistanceRepsProcessor.java:117-128
  *   gdist_sketch_build     SequenceKmers.hashSet(width)          SketchProcessor.java:88, WidthProcessor.java:178
  *   gdist_sketch_matrix    Sketch.distance(other) all-pairs      WidthProcessor.java:183-185, TuningProcessor.java:131-133
+ *   gdist_closest          getClosest(kmers, n, maxDist), exhaustively
+ *                          (every column, no LSH buckets)        MashProcessor.java:150, FindProcessor.java:110
+ *                          --maxDist of the genomes table        GenomeProcessor.java:58-60,89
  *   gdist_sets_allgather   (new) RCCL all-gather of packed sets for row-sharded N×N
  *
  * Kmer code spec (shared by the device packer, the CPU oracle in oracle/ and
@@ -357,6 +360,38 @@ int  gdist_lsh_free(gdist_lsh* lsh);
  * (ties by index), at most n: idx_out[q*n + r], d_out[q*n + r], count_out[q]. */
 int  gdist_lsh_closest(gdist_ctx* ctx, const gdist_lsh* lsh, const gdist_sets* queries, int n, double max_dist,
                        int64_t* idx_out, double* d_out, int32_t* count_out);
+
+/* ---- exact nearest neighbours ----------------------------------------- */
+/* getClosest(kmers, n, maxDist) (MashProcessor.java:150, FindProcessor.java:110)
+ * over every column instead of the LSH buckets: for every query set q in
+ * [r0, r1) the columns j in [c0, c1) with d(q, j) <= max_dist (j = q excluded
+ * unless GDIST_CLOSEST_KEEP_SELF), ordered by (d ascending as fp64, j
+ * ascending), the first n of them. Host outputs laid out as gdist_lsh_closest:
+ * idx_out[(q-r0)*n + r] the global set index of the r-th neighbour,
+ * d_out[(q-r0)*n + r] its distance, count_out[q-r0] the neighbours found;
+ * slots at or past the count are -1 / 1.0. d is bit-identical to the D of
+ * gdist_intersect_matrix (kmer sets: method AUTO / SORTED / BITSET) or
+ * gdist_sketch_matrix (GDIST_SKETCH collections: method ignored,
+ * GDIST_SKETCH_JACCARD honoured) with the same flags; NaN (GDIST_EMPTY_NAN)
+ * never qualifies, d == 1.0 does when max_dist >= 1.0 (a plain <=, not the
+ * ARGMIN identity rule). Queries against other subjects (M×N): one collection
+ * through gdist_sets_concat. The N×N never leaves the device: row blocks x
+ * column chunks (options "closest_rows" / "closest_cols", defaults by memory)
+ * are selected from as the matrix kernels produce them, and for kmer sets D
+ * is never written. n == 0 or an empty range: GDIST_OK, counts 0. EINVAL:
+ * n < 0 or n > GDIST_CLOSEST_MAX_N, NaN max_dist, GDIST_UPPER_TRIANGLE or
+ * GDIST_OUT_DEVICE (not supported), SORTED on a bitsets-only collection. */
+#define GDIST_CLOSEST_KEEP_SELF 0x1000u   /* a query in [c0, c1) may be its own neighbour */
+#define GDIST_CLOSEST_MAX_N     512
+int  gdist_closest(gdist_ctx* ctx, const gdist_sets* sets,
+                   int64_t r0, int64_t r1, int64_t c0, int64_t c1,
+                   int method, unsigned flags, int n, double max_dist,
+                   int64_t* idx_out, double* d_out, int32_t* count_out);
+/* HIP-event time (ms, summed over the steps, on the context's stream) of the
+ * last gdist_closest call made with option "time_kernels" = 1: the matrix
+ * kernels (intersect or sketch) and the select kernel apart; -1 when the
+ * call was not timed. */
+int  gdist_ctx_closest_timing(gdist_ctx* ctx, double* matrix_ms, double* select_ms);
 
 /* ---- multi-GPU (RCCL over xGMI) -------------------------------------- */
 #define GDIST_UNIQUE_ID_BYTES 128

@@ -15,6 +15,7 @@ public final class GpuKmerSets implements AutoCloseable {
     public static final int DNA = 0, PROT = 1;
     public static final int METHOD_AUTO = 0, METHOD_SORTED = 1, METHOD_BITSET = 2;
     public static final int UPPER_TRIANGLE = 0x100;
+    public static final int CLOSEST_KEEP_SELF = 0x1000, CLOSEST_MAX_N = 512;
 
     static native long nCtxCreate(int device);
     static native void nCtxDestroy(long ctx);
@@ -40,6 +41,8 @@ public final class GpuKmerSets implements AutoCloseable {
     static native long nSketchUpload(long ctx, int width, long[] off, int[] sigs);
     static native void nSketchMatrix(long ctx, long sk, long r0, long r1, long c0, long c1, int flags,
                                      double[] out, int ld);
+    static native void nClosest(long ctx, long sets, long r0, long r1, long c0, long c1, int method, int flags,
+                                int n, double maxDist, long[] idx, double[] d, int[] count);
 
     /** One device context (gdist_ctx): serialises its calls, shared by threads. */
     public static final class Context implements AutoCloseable {
@@ -104,6 +107,18 @@ public final class GpuKmerSets implements AutoCloseable {
     /** argmin over cols (DistanceRepsProcessor.java:238-239): the position in cols,
      *  -1 when none is below 1.0; bestD[0] = its distance */
     public int closest(long q, long[] cols, double[] bestD) { return nArgmin(ctx, handle, q, cols, bestD); }
+
+    /** getClosest(kmers, n, maxDist) of every set in [r0, r1) over every column in
+     *  [c0, c1) (MashProcessor.java:150, FindProcessor.java:110; exhaustive, no LSH
+     *  buckets; gdist_closest): idx[(q - r0) * n + r] / d[...] = the r-th nearest set
+     *  with distance <= maxDist and its distance (ties by index), count[q - r0] how
+     *  many were found; unused slots are -1 / 1.0. The set itself is left out unless
+     *  keepSelf. Works on kmer sets and on sketch collections. */
+    public void closest(long r0, long r1, long c0, long c1, int n, double maxDist, boolean keepSelf,
+                        long[] idx, double[] d, int[] count) {
+        nClosest(ctx, handle, r0, r1, c0, c1, METHOD_AUTO, keepSelf ? CLOSEST_KEEP_SELF : 0, n, maxDist, idx, d,
+                 count);
+    }
 
     /** Both passes of DistanceRepsProcessor.java:185-262 in one call: isRep[i] = 1
      *  for representatives (in set order, greedy); repOf / repDist = each set's

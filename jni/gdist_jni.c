@@ -389,3 +389,30 @@ JNIEXPORT void JNICALL JFN(nSketchMatrix)(JNIEnv* env, jclass c, jlong ctx, jlon
     free(d);
     if (rc) throw_for(env, rc);
 }
+
+/* ---- exact nearest neighbours: getClosest(kmers, n, maxDist) over every column
+ * (MashProcessor.java:150, FindProcessor.java:110); idx / d hold (r1 - r0) * n
+ * entries, count r1 - r0 (gdist_closest) */
+JNIEXPORT void JNICALL JFN(nClosest)(JNIEnv* env, jclass c, jlong ctx, jlong sets, jlong r0, jlong r1, jlong c0,
+                                     jlong c1, jint method, jint flags, jint n, jdouble maxDist, jlongArray idx,
+                                     jdoubleArray d, jintArray count) {
+    const int64_t nr = (int64_t)r1 - (int64_t)r0;
+    if (nr < 0 || n < 0) { throw_arg(env, "negative row range or n"); return; }
+    const int64_t cells = nr * (int64_t)n;
+    if (too_short(env, idx, cells, "idx shorter than (r1 - r0) * n") ||
+        too_short(env, d, cells, "d shorter than (r1 - r0) * n") ||
+        too_short(env, count, nr, "count shorter than r1 - r0"))
+        return;
+    int64_t* vi = malloc(((size_t)cells + 1) * sizeof(int64_t));
+    double* vd = malloc(((size_t)cells + 1) * sizeof(double));
+    int32_t* vc = malloc(((size_t)nr + 1) * sizeof(int32_t));
+    if (!vi || !vd || !vc) { free(vi); free(vd); free(vc); throw_oom(env); return; }
+    int rc = gdist_closest(CTX(ctx), SETS(sets), r0, r1, c0, c1, method, (unsigned)flags, n, maxDist, vi, vd, vc);
+    if (!rc) {
+        (*env)->SetLongArrayRegion(env, idx, 0, (jsize)cells, (const jlong*)vi);
+        (*env)->SetDoubleArrayRegion(env, d, 0, (jsize)cells, vd);
+        (*env)->SetIntArrayRegion(env, count, 0, (jsize)nr, (const jint*)vc);
+    }
+    free(vi); free(vd); free(vc);
+    if (rc) throw_for(env, rc);
+}
