@@ -2624,7 +2624,7 @@ static MatrixPlan& matrix_plan(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, 
                                    ctx->option(OPT_BITSET_MFMA_GROUP, 0),
                                    ctx->option(OPT_SPARSE_RARE, 1), ctx->option(OPT_SPARSE_CHUNKS, -1),
                                    ctx->option(OPT_SPARSE_PART_BUDGET, -1), ctx->option(OPT_SPARSE_WG_PER_CU, -1),
-                                   ctx->option(OPT_SPARSE_XCD, 0)};
+                                   ctx->option(OPT_SPARSE_XCD, 0), ctx->option(OPT_SPARSE_BALANCE, kSparseBalanceDefault)};
     auto it = s->plans.find(key);
     if (it == s->plans.end()) {
         if (s->plans.size() >= 8) {   // row-block loops: keep the cache small

@@ -134,7 +134,13 @@ inline void d2h(void* dst, const void* src, size_t bytes, hipStream_t s) {
 struct SparseScratch {
     bool ready = false;
     DevBuf tiles, part;   // tile list, per-chunk counters
-    DevBuf bounds;        // int32 [nchunks + 1]: first sparse word of each chunk (cost-balanced)
+    // int32 bounds tables, first sparse word of each chunk: table 0 for the
+    // off-diagonal tiles (nchunks + 1 entries), then (balanced plans) the
+    // diagonal tiles' table with half as many chunks
+    DevBuf bounds;
+    DevBuf tinfo;         // int4 [ntiles]: {its table's first entry, its chunks, its first partial, 0}
+    DevBuf wgmap;         // int2 [total_chunks]: workgroup -> (tile, chunk), heaviest first (null: tile-major)
+    int64_t total_chunks = 0;   // sum over the tiles of their chunks: tile workgroups and partials
     // the rare tier's pairs are recounted every step by the sparse tile
     // launch's leading workgroups into a per-tile slab the chunk reduce adds
     // (sparse.hip rare_slab_row): the region's (row block, column block) ->
@@ -142,7 +148,7 @@ struct SparseScratch {
     DevBuf rare_tile, rare_slab;
     int64_t rare_ab0 = 0, rare_nbc = 0;
     bool rare_in = false;
-    int nchunks = 0;
+    int nchunks = 0;         // chunks of an off-diagonal tile (the most any tile has)
     bool use_part = false;   // chunks store partials (else flush with atomics)
     int64_t ntiles = 0;
 };
@@ -260,7 +266,8 @@ struct Timing {
     X(SERIAL_STEP, "serial_step")             /* 1: the side stream's kernel families on the main stream, in turn (timing) */ \
     X(SPLIT_BUILD, "split_build")             /* gathered collection on R ranks: each builds 1/R and all-gathers (default); 0 every rank all; k >= 2 without peers: k shares in turn here */ \
     X(CLOSEST_ROWS, "closest_rows")           /* gdist_closest: query rows a block (default: by memory) */ \
-    X(CLOSEST_COLS, "closest_cols")           /* gdist_closest: columns a chunk (default: by memory) */
+    X(CLOSEST_COLS, "closest_cols")           /* gdist_closest: columns a chunk (default: by memory) */ \
+    X(SPARSE_BALANCE, "sparse_balance")       /* sparse chunks: 0 equal word counts, tile-major; 1 equal modelled cost, 3/4 as many for diagonal tiles, heaviest workgroups first; 2 (default) the same with costs tapering along a tile's chunks, two rounds of workgroups */
 
 enum Opt : int {
 #define GDIST_OPT_ENUM(id, name) OPT_##id,
@@ -419,6 +426,7 @@ struct gdist_sets {
     int64_t sp_groups = 0, sp_group_words = 0;
     std::vector<int32_t> sp_bucket_bits;  // [nsets][sp_nbk]: complement bits per set and 1024 sparse words
     int64_t sp_nbk = 0;
+    std::vector<double> sp_cost;          // products z (z - 1) / 2 per granule of 16 sparse words (sparse_bounds.hpp)
     // summaries of the pack chunks (option pack_summary): the code-major pack
     // sort leaves each chunk's codes in code order, so their runs are that
     // chunk's summary; local_summary merges them instead of re-sorting codes
@@ -573,6 +581,7 @@ constexpr int kGuides = 8;                       // guide sequences per packed c
                                                  // clades: 2 -> 8 guides took the step 4.60 -> 3.25 ms; C2 and
                                                  // pack time unchanged, profiles/r02/realistic/guides.txt)
 constexpr double kSparseProductsPerS = 6.5e11;   // sparse tiles (v6): complement-word products (C2)
+constexpr int kSparseBalanceDefault = 2;         // option sparse_balance (sparse.hip sparse_plan)
 constexpr double kSparseItemsPerS = 1.0e11;      // sparse tiles (v6): (tile, sparse word) visits (C2)
 bool locus_order_enabled(const gdist_ctx* ctx);  // option locus_order = 0 keeps code order (A/B)
 // key[r] = tag | guide position of dense rank r; kmers no guide holds sort

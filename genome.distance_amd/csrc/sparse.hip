@@ -30,6 +30,7 @@
 #include <cstring>
 
 #include "gdist_internal.hpp"
+#include "sparse_bounds.hpp"
 
 namespace gdist {
 namespace {
@@ -922,7 +923,8 @@ __device__ __forceinline__ void global_batch(const TileWalk& tc, int64_t s0, int
 template <int SUN, int MT>
 __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
     const int64_t* __restrict__ off, const ulonglong2* __restrict__ ent, const int32_t* __restrict__ nc, int64_t Us,
-    int64_t Ws, const int2* __restrict__ tiles, const int32_t* __restrict__ cbnd, int nchunks, int64_t r0, int64_t r1,
+    int64_t Ws, const int2* __restrict__ tiles, const int32_t* __restrict__ cbnd, const int4* __restrict__ tinfo,
+    const int2* __restrict__ wgmap, int nchunks, int64_t r0, int64_t r1,
     int64_t c0, int64_t c1, int upper, int32_t* __restrict__ I, int64_t ldI, int32_t* __restrict__ part, int64_t Wdp,
     int64_t N, const unsigned long long* __restrict__ slab_bits, int slabs, GroupPart gp, int xmap, int ntiles,
     RareSlab rs, int dyn, int diag22, int rpart22) {
@@ -943,7 +945,13 @@ __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
     }
     const unsigned bid = blockIdx.x;
     int tile, ch;
-    if (xmap) {
+    if (wgmap) {
+        // the plan's order: heaviest modelled (tile, chunk) first, so that
+        // the launch's last tile workgroups are its shortest
+        const int2 m = wgmap[bid];
+        tile = m.x;
+        ch = m.y;
+    } else if (xmap) {
         // option sparse_xcd: workgroup b = 8 (t + ntiles g) + x runs chunk
         // 8 g + x of tile t. Workgroups are dealt to the 8 XCDs round-robin,
         // so chunk c of every tile runs on XCD c mod 8, the tiles of one
@@ -958,6 +966,10 @@ __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
         ch = (int)(bid % (unsigned)nchunks);
     }
     const int64_t A = tiles[tile].x, B = tiles[tile].y;
+    // the tile's bounds table and first partial (diagonal tiles of a balanced
+    // plan have a table of their own with half as many chunks)
+    const int4 ti = tinfo[tile];
+    cbnd += ti.x;
     const int rlo = (int)(r0 - A * SB > 0 ? r0 - A * SB : 0);
     const int rhi = (int)(r1 - A * SB < SB ? r1 - A * SB : SB);
     // rows trimmed only where the region cuts a block's existing rows: the
@@ -1033,7 +1045,7 @@ __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
     }
     __syncthreads();
     if (part) {
-        uint32_t* dst = reinterpret_cast<uint32_t*>(part) + ((int64_t)tile * nchunks + ch) * (SB * SB / 2);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(part) + ((int64_t)ti.z + ch) * (SB * SB / 2);
         for (int t = threadIdx.x; t < SB * SB / 2; t += SNT) dst[t] = cnt[t];
         return;
     }
@@ -1058,7 +1070,8 @@ __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
 // workgroup per CU, 62 loads per lane in a chain, ran at ~2 TB/s).
 constexpr int kReduceCnt = 8;
 constexpr int kReduceGroups = 64;                            // 16-byte groups per workgroup
-__global__ __launch_bounds__(256) void sparse_reduce_kernel(const int32_t* __restrict__ part, int nchunks,
+__global__ __launch_bounds__(256) void sparse_reduce_kernel(const int32_t* __restrict__ part,
+                                                            const int4* __restrict__ tinfo,
                                                             const int2* __restrict__ tiles,
                                                             const int32_t* __restrict__ nc, int64_t Us, int64_t r0,
                                                             int64_t r1, int64_t c0, int64_t c1, int upper,
@@ -1073,7 +1086,9 @@ __global__ __launch_bounds__(256) void sparse_reduce_kernel(const int32_t* __res
     const int tile = blockIdx.x / per_tile;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int g = (blockIdx.x % per_tile) * kReduceGroups + lane;        // 16-byte group of the tile's counters
-    const uint4* p = reinterpret_cast<const uint4*>(part) + (int64_t)tile * nchunks * (SB * SB / 8) + g;
+    const int4 ti = tinfo[tile];                                         // {-, the tile's chunks, its first partial, -}
+    const int nchunks = ti.y;
+    const uint4* p = reinterpret_cast<const uint4*>(part) + (int64_t)ti.z * (SB * SB / 8) + g;
     uint32_t acc[kReduceCnt] = {0, 0, 0, 0, 0, 0, 0, 0};
     auto add = [&](const uint4& v) {
         acc[0] += v.x & 0xFFFFu; acc[1] += v.x >> 16;
@@ -1190,6 +1205,7 @@ void free_sparse(gdist_sets* s) {
     s->Wd = s->Ws = s->sp_entries = s->sp_U = 0;
     s->sp_bucket_bits.clear();
     s->sp_nbk = 0;
+    s->sp_cost.clear();
     s->sp_pos_words = 0;
     s->sp_fold_dense = false;
     s->sp_fold_slabs = 0;
@@ -1461,6 +1477,12 @@ void build_sparse_words(gdist_ctx* ctx, gdist_sets* s) {
         s->sp_bucket_bits.assign((size_t)N * nbk, 0);
         d2h(s->sp_bucket_bits.data(), dbb.p, (size_t)N * nbk * 4, st);
     }
+    {   // the products of the sparse words per granule, for the plan's chunk
+        // bounds at equal cost (z is on the host already: no copy of its own)
+        std::vector<int32_t> zs(Ws);
+        for (int64_t k = 0; k < Ws; k++) zs[k] = z[sw[k]];
+        s->sp_cost = sparse_granule_costs(zs.data(), Ws);
+    }
     GD_HIP(hipGetLastError());
     s->sp_ent.alloc((total + kSentinelRecs) * 16, st);
     GD_HIP(hipMemsetAsync(s->sp_ent.as<ulonglong2>() + total, 0, kSentinelRecs * 16, st));   // the sentinel run
@@ -1571,41 +1593,108 @@ void sparse_plan(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, in
         // chunks that fold a dense-word slab (the first sp_fold_slabs) hold
         // at most kChunkWords - kFoldSlabWords words: every chunk does
         const int64_t cap = s->sp_fold_slabs ? kChunkWords - kFoldSlabWords : kChunkWords;
-        // chunk bounds at equal word counts (n chunks)
-        auto make_bounds = [&](int64_t n) {
-            std::vector<int32_t> b;
-            for (int64_t c = 0; c <= n; c++) b.push_back((int32_t)(s->Ws * c / n));
-            return b;
-        };
         // A chunk is exact when it holds <= kChunkWords words (64 x 1023 <
         // 2^16 whatever the sets) or when the SECOND largest set total of
         // complement bits over the buckets covering it is <= 65535 (one set
         // may hold more: a guide lacks every kmer the later guides key, C2's
         // sets 0-3); sp_bucket_bits holds the totals per set and bucket of
         // 1024 sparse words.
-        auto bounds_ok = [&](const std::vector<int32_t>& b) {
+        auto chunk_ok = [&](int64_t b0, int64_t b1, int64_t c) {
             const int64_t N = s->nsets, nbk = s->sp_nbk;
-            if ((int64_t)b.size() - 1 < s->sp_fold_slabs) return false;    // a chunk per slab
-            for (size_t c = 0; c + 1 < b.size(); c++) {
-                const int64_t b0 = b[c], b1 = b[c + 1];
-                const int64_t fold = (int64_t)c < s->sp_fold_slabs ? 64 * kFoldSlabWords : 0;
-                if (b1 - b0 <= cap) continue;
-                if ((int64_t)s->sp_bucket_bits.size() != N * nbk) return false;
-                int64_t m1 = 0, m2 = 0;
-                for (int64_t i = 0; i < N; i++) {
-                    int64_t t = 0;
-                    for (int64_t k = b0 >> kBucketShift; k <= (b1 - 1) >> kBucketShift; k++)
-                        t += s->sp_bucket_bits[i * nbk + k];
-                    if (t > m1) { m2 = m1; m1 = t; } else if (t > m2) m2 = t;
-                }
-                if (m2 + fold > 65535) return false;
+            const int64_t fold = c < s->sp_fold_slabs ? 64 * kFoldSlabWords : 0;
+            if (b1 - b0 <= cap) return true;
+            if ((int64_t)s->sp_bucket_bits.size() != N * nbk) return false;
+            int64_t m1 = 0, m2 = 0;
+            for (int64_t i = 0; i < N; i++) {
+                int64_t t = 0;
+                for (int64_t k = b0 >> kBucketShift; k <= (b1 - 1) >> kBucketShift; k++)
+                    t += s->sp_bucket_bits[i * nbk + k];
+                if (t > m1) { m2 = m1; m1 = t; } else if (t > m2) m2 = t;
             }
+            return m2 + fold <= 65535;
+        };
+        auto bounds_ok = [&](const std::vector<int32_t>& b) {
+            if ((int64_t)b.size() - 1 < s->sp_fold_slabs) return false;    // a chunk per slab
+            for (size_t c = 0; c + 1 < b.size(); c++)
+                if (!chunk_ok(b[c], b[c + 1], (int64_t)c)) return false;
             return true;
+        };
+        // Modelled cost of the sparse words per granule, in products: the
+        // words' products (kept at build time) + kVisitProducts per word and
+        // tile (whole-triangle figures, as sp_products / sp_items). A word
+        // with z holders costs z (z - 1) / 2 products and the locus order
+        // puts the expensive words last: on C2 the last of 62 equal-count
+        // chunks holds 2.2x the mean products. Its workgroups run 1.55x the
+        // mean (50 us against 32, the second last 39; every other chunk
+        // within 1 us of 32: profiles/r07/timeline_c2.json), so a word's
+        // visit (its offsets, its share of a batch's prefix sums and record
+        // setup) weighs as much as ~40 products of the tile.
+        // (the XCD-mapped launch, option sparse_xcd, stays as it was: equal
+        // counts, one table, its own order)
+        const bool xcd = ctx->option(OPT_SPARSE_XCD, 0) != 0;
+        const int64_t bal = xcd ? 0 : ctx->option(OPT_SPARSE_BALANCE, kSparseBalanceDefault);
+        const bool balance = bal != 0;
+        constexpr double kVisitProducts = 40.0;
+        const double visit = (double)ceil_div(s->nsets, SB) * (double)(ceil_div(s->nsets, SB) + 1) / 2 * kVisitProducts;
+        std::vector<double> gcost = s->sp_cost;
+        for (size_t g = 0; g < gcost.size(); g++)
+            gcost[g] += visit * (double)std::min<int64_t>(kCostGranule, s->Ws - (int64_t)g * kCostGranule);
+        // chunk bounds (n chunks): at equal modelled cost (option
+        // sparse_balance, default; a chunk that would not be exact is split,
+        // so more than n may come back), or at equal word counts
+        // Tapered chunks (sparse_balance 2, default): a tile's chunk costs
+        // fall in a line from 1 + kTaper to 1 - kTaper of their mean. The
+        // launch's last workgroups are then its shortest, and its tail (the
+        // time from the first idle wave slot to the last workgroup's end:
+        // with chunks of one size about one workgroup's run, 35 of C2's 98 us)
+        // is the length of those. C2, 62 chunks: taper 0.4 / 0.6 / 0.8 ran
+        // 0.1065 / 0.1027 / 0.1018 ms a step (equal counts 0.1141, equal
+        // costs without taper 0.1106); 56 chunks: 0.8 / 0.9 ran 0.1025 /
+        // 0.1055: past 0.8 the first workgroups run as long as the whole
+        // launch (profiles/r07/ab_c2.txt).
+        constexpr double kTaper = 0.8;
+        auto taper = [&](int64_t n) {
+            std::vector<double> w;
+            if (bal >= 2 && n > 1)
+                for (int64_t k = 0; k < n; k++) w.push_back(1.0 + kTaper * (1.0 - 2.0 * (double)k / (double)(n - 1)));
+            return w;
+        };
+        auto make_bounds = [&](int64_t n) {
+            if (!balance) return equal_count_bounds(s->Ws, n);
+            n = std::max<int64_t>(std::max<int64_t>(n, s->sp_fold_slabs), 1);
+            return balanced_bounds(gcost, s->Ws, n, s->sp_fold_slabs, cap, chunk_ok, taper(n));
+        };
+        // a table's modelled chunk costs: max / mean and the chunk holding the max
+        auto chunk_costs = [&](const std::vector<int32_t>& b) {
+            std::vector<double> c;
+            for (size_t k = 0; k + 1 < b.size(); k++) c.push_back(range_cost(gcost, s->Ws, b[k], b[k + 1]));
+            return c;
+        };
+        auto skew = [&](const std::vector<double>& c, int& at) {
+            double mx = 0.0, sum = 0.0;
+            at = 0;
+            for (size_t k = 0; k < c.size(); k++) {
+                sum += c[k];
+                if (c[k] > mx) { mx = c[k]; at = (int)k; }
+            }
+            return sum > 0.0 ? mx * (double)c.size() / sum : 1.0;
         };
         std::vector<int32_t> bnd;
         if (sc.ntiles) {
             int64_t n0 = std::max<int64_t>(std::max<int64_t>(ceil_div(s->Ws, cap), s->sp_fold_slabs),
                                            std::min<int64_t>(ceil_div(s->Ws, 512), ceil_div(target, sc.ntiles)));
+            // Tapered chunks need not stay under the word cap (a longer one
+            // is checked against the sets' bits and split if it must be), and
+            // fewer of them store and reduce fewer partials: two rounds of
+            // the chip's workgroup slots, so that the longest workgroups, all
+            // in the first round, end well before the launch does; at most
+            // as many as above and at least half. C2 (36 tiles, 1024 slots)
+            // tapered: 40 / 44 / 48 / 56 / 62 chunks ran 0.120 / 0.114 /
+            // 0.099-0.108 / 0.102 / 0.102 ms a step: under 1.7 rounds the
+            // first workgroups are the launch's critical path, so 2 (57).
+            if (bal >= 2)
+                n0 = std::max<int64_t>(std::max<int64_t>((n0 + 1) / 2, s->sp_fold_slabs),
+                                       std::min<int64_t>(n0, ceil_div(2 * target, sc.ntiles)));
             bnd = make_bounds(n0);
             // Past the partial budget (many tiles: N >> 1000), fewer and
             // longer chunks where the complement bits allow it (bounds_ok), so
@@ -1614,13 +1703,14 @@ void sparse_plan(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, in
             if (sc.ntiles * nb0 * tile_bytes > budget) {
                 for (int64_t fewer = std::max<int64_t>(1, budget / (sc.ntiles * tile_bytes)); fewer < nb0; fewer *= 2) {
                     auto b = make_bounds(fewer);
-                    if (bounds_ok(b)) { bnd = b; break; }
+                    // (balanced bounds split a chunk that would not be exact: still within the budget?)
+                    if (bounds_ok(b) && sc.ntiles * ((int64_t)b.size() - 1) * tile_bytes <= budget) { bnd = b; break; }
                 }
             }
             // XCD-mapped order (option sparse_xcd): whole groups of 8 chunks, so
             // every XCD gets the same number of chunks of every tile
             const int64_t nb1 = (int64_t)bnd.size() - 1;
-            if (ctx->option(OPT_SPARSE_XCD, 0) != 0 && nb1 > 8 && nb1 % 8) {
+            if (xcd && nb1 > 8 && nb1 % 8) {
                 auto b = make_bounds(ceil_div(nb1, 8) * 8);
                 if (bounds_ok(b)) bnd = b;
             }
@@ -1631,25 +1721,129 @@ void sparse_plan(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, in
         }
         const int64_t nch = sc.ntiles ? (int64_t)bnd.size() - 1 : 0;
         sc.nchunks = (int)nch;
+        // A diagonal tile walks half an off-diagonal tile's products (the
+        // pairs x < y of one list) but visits every word all the same, and
+        // zeroes, stores and has the reduce read back 32 KiB per chunk: its
+        // workgroups run ~0.75 of an off-diagonal tile's over the same words
+        // (C2: 24-26 us against 32), so balanced plans give it a table of
+        // its own with three quarters as many chunks, never below the fold's
+        // slabs. (Half as many made them the launch's longest: C2 tapered,
+        // 48 chunks, 0.108 ms a step against 0.099.)
+        auto is_diag = [&](const int2& t) {      // as the tile kernel decides it
+            const int64_t rlo = std::max<int64_t>(r0 - (int64_t)t.x * SB, 0);
+            const int64_t rhi = std::min<int64_t>(r1 - (int64_t)t.x * SB, SB);
+            return t.x == t.y && !(rlo > 0 || (rhi < SB && r1 < s->nsets));
+        };
+        // Tiles with counts of their own need the workgroup map below; very
+        // large grids keep one count and tile-major order: their tail is a
+        // small part of the launch, and sorting the map is host time.
+        constexpr int64_t kOrderMax = int64_t(1) << 20;
+        const bool ordered = sc.ntiles && balance && nch > 1 && sc.ntiles * nch <= kOrderMax;
+        auto diag_share = [&](int64_t n) { return (n * 3 + 3) / 4; };
+        std::vector<int32_t> bnd_d;
+        if (ordered) {
+            const int64_t nd = std::max<int64_t>(std::max<int64_t>(diag_share(nch), s->sp_fold_slabs), 1);
+            bool any = false;
+            for (const int2& t : tiles) any = any || is_diag(t);
+            if (any && nd < nch) {
+                bnd_d = make_bounds(nd);
+                if ((int64_t)bnd_d.size() - 1 >= nch) bnd_d.clear();       // split back up to the full count
+                else GD_REQUIRE(bounds_ok(bnd_d), "sparse chunks exceed the 16-bit counter bound");
+            }
+        }
+        const int64_t nch_d = bnd_d.empty() ? nch : (int64_t)bnd_d.size() - 1;
+        // per tile: {its table's first entry, its chunks, its first partial}
+        std::vector<int4> tinfo((size_t)sc.ntiles);
+        sc.total_chunks = 0;
+        for (int64_t t = 0; t < sc.ntiles; t++) {
+            const bool d = !bnd_d.empty() && is_diag(tiles[t]);
+            GD_REQUIRE(sc.total_chunks < (int64_t(1) << 31) - nch, "sparse grid too large");
+            tinfo[t] = make_int4(d ? (int)bnd.size() : 0, (int)(d ? nch_d : nch), (int)sc.total_chunks, 0);
+            sc.total_chunks += d ? nch_d : nch;
+        }
+        const std::vector<double> cc = chunk_costs(bnd);
+        // Launch order (balanced plans): workgroups are dispatched in grid
+        // order, so the heaviest modelled (tile, chunk) goes first and the
+        // last to start are the lightest: a chunk's cost times its tile's
+        // weight (half on the diagonal; by the rows a trimmed tile or the
+        // collection's last, partial block keeps, and that block's columns).
+        // Costs are compared in eighths of the mean and ties keep tile-major
+        // order: balanced chunks differ by a few per cent, and ordering by
+        // those would deal the tiles of one chunk out together (C2 has its
+        // heavy tiles, block 0 holding the guides, first in tile-major order
+        // and its lightest, the partial diagonal one, last).
+        sc.wgmap.release();
+        if (ordered) {
+            struct Wg { double cost; int tile, ch; };
+            std::vector<Wg> wg;
+            wg.reserve((size_t)sc.total_chunks);
+            for (int64_t t = 0; t < sc.ntiles; t++) {
+                const int64_t A = tiles[t].x, B = tiles[t].y;
+                const int64_t rows = std::min<int64_t>(std::min<int64_t>(r1, s->nsets), (A + 1) * SB) - std::max<int64_t>(r0, A * SB);
+                const int64_t cols = std::min<int64_t>(s->nsets, (B + 1) * SB) - B * SB;
+                const bool d = is_diag(tiles[t]);
+                const double wt = (d ? 0.5 : 1.0) * (double)rows / SB * (double)cols / SB;
+                const std::vector<int32_t>& b = tinfo[t].x ? bnd_d : bnd;
+                // every word is visited whatever the tile holds; its products go by the tile's share
+                for (int ch = 0; ch < tinfo[t].y; ch++)
+                    wg.push_back(Wg{visit * (double)(b[(size_t)ch + 1] - b[(size_t)ch]) +
+                                        wt * range_cost(s->sp_cost, s->Ws, b[(size_t)ch], b[(size_t)ch + 1]),
+                                    (int)t, ch});
+            }
+            double mean = 0.0;
+            for (const Wg& w : wg) mean += w.cost / (double)wg.size();
+            if (mean > 0.0)
+                for (Wg& w : wg) w.cost = std::floor(w.cost / mean * 8.0 + 0.5);
+            std::stable_sort(wg.begin(), wg.end(), [](const Wg& a, const Wg& b) { return a.cost > b.cost; });
+            std::vector<int2> map;
+            map.reserve(wg.size());
+            for (const Wg& w : wg) map.push_back(make_int2(w.tile, w.ch));
+            sc.wgmap.alloc(map.size() * sizeof(int2), st);
+            h2d(sc.wgmap.p, map.data(), map.size() * sizeof(int2), st);
+        }
         if (sc.ntiles) {
             sc.tiles.alloc(sc.ntiles * sizeof(int2), st);
             h2d(sc.tiles.p, tiles.data(), sc.ntiles * sizeof(int2), st);
-            sc.bounds.alloc(bnd.size() * 4, st);
-            h2d(sc.bounds.p, bnd.data(), bnd.size() * 4, st);
+            std::vector<int32_t> tables = bnd;
+            tables.insert(tables.end(), bnd_d.begin(), bnd_d.end());
+            sc.bounds.alloc(tables.size() * 4, st);
+            h2d(sc.bounds.p, tables.data(), tables.size() * 4, st);
+            sc.tinfo.alloc(tinfo.size() * sizeof(int4), st);
+            h2d(sc.tinfo.p, tinfo.data(), tinfo.size() * sizeof(int4), st);
         }
         // chunk partials (16-bit counters, 32 KiB per tile and chunk) within a
         // byte budget (option sparse_part_budget, default 1 GiB); past it the
         // chunks flush their counters with global atomics instead
-        const int64_t part_bytes = sc.ntiles * sc.nchunks * tile_bytes;
+        const int64_t part_bytes = sc.total_chunks * tile_bytes;
         sc.use_part = sc.nchunks > 1 && part_bytes <= budget;
         if (sc.use_part) sc.part.alloc((size_t)part_bytes, st);
-        if (ctx->trace())
+        if (ctx->trace()) {
             fprintf(stderr, "gdist: sparse plan rows [%lld,%lld) cols [%lld,%lld): %lld tiles x %d chunks, %s, "
                             "%lld of %lld sparse words positive\n",
                     (long long)r0, (long long)r1, (long long)c0, (long long)c1, (long long)sc.ntiles, sc.nchunks,
                     sc.use_part ? "partials" : "atomic flush", (long long)s->sp_pos_words,
                     (long long)s->Ws);
-        GD_REQUIRE(sc.ntiles * sc.nchunks < (int64_t(1) << 31), "sparse grid too large");
+            if (sc.ntiles) {
+                // the plan's modelled cost per chunk against equal word counts
+                // of the same number of chunks
+                const std::vector<int32_t> eq = equal_count_bounds(s->Ws, nch);
+                int at = 0, at_eq = 0, moved = 0;
+                // (tapered chunks: each cost against its own share)
+                std::vector<double> rel = cc;
+                const std::vector<double> tw = taper(nch);
+                if (tw.size() == rel.size())
+                    for (size_t k = 0; k < rel.size(); k++) rel[k] /= tw[k];
+                const double sk = skew(rel, at), sk_eq = skew(chunk_costs(eq), at_eq);
+                for (size_t k = 0; k < bnd.size(); k++) moved += bnd[k] != eq[k];
+                fprintf(stderr, "gdist: sparse chunks %s%s: %lld a tile (%lld on the diagonal), %lld workgroups %s; "
+                                "modelled cost max / mean %.3f (chunk %d), at equal counts %.3f (chunk %d); "
+                                "%d of %lld bounds differ\n",
+                        balance ? "balanced" : "at equal counts", bal >= 2 ? " (tapered)" : "", (long long)nch, (long long)nch_d,
+                        (long long)sc.total_chunks, sc.wgmap.p ? "heaviest first" : "tile-major", sk, at, sk_eq,
+                        at_eq, moved, (long long)bnd.size());
+            }
+        }
+        GD_REQUIRE(sc.total_chunks < (int64_t(1) << 31), "sparse grid too large");
         if (sc.use_part) rare_slab_plan(ctx, s, r0, r1, tiles, sc);
         sc.ready = true;
     }
@@ -1702,10 +1896,11 @@ bool sparse_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
         rs.ab0 = sc.rare_ab0;
         rs.nbc = sc.rare_nbc;
     }
-    const int64_t grid = (xmap ? ceil_div(nchunks, 8) * 8 * nt : nt * nchunks) + rs.nrare;
+    const int64_t grid = (xmap ? ceil_div(nchunks, 8) * 8 * nt : sc.total_chunks) + rs.nrare;
     GD_REQUIRE(grid < (int64_t(1) << 31), "sparse grid too large");
     kern<<<(unsigned)grid, SNT, 0, st>>>(s->sp_off.as<int64_t>(), s->sp_ent.as<ulonglong2>(), s->sp_nc.as<int32_t>(),
-                                         s->sp_U, s->Ws, sc.tiles.as<int2>(), sc.bounds.as<int32_t>(), nchunks, r0, r1,
+                                         s->sp_U, s->Ws, sc.tiles.as<int2>(), sc.bounds.as<int32_t>(),
+                                         sc.tinfo.as<int4>(), sc.wgmap.as<int2>(), nchunks, r0, r1,
                                          c0, c1, upper ? 1 : 0, d_I, ldI, sc.use_part ? sc.part.as<int32_t>() : nullptr,
                                          s->Wd, s->nsets, s->dbits.as<unsigned long long>(), s->sp_fold_slabs,
                                          group_part(s), xmap ? 1 : 0, (int)nt, rs,
@@ -1715,7 +1910,8 @@ bool sparse_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
     ft.end();
     if (sc.use_part) {
         sparse_reduce_kernel<<<(unsigned)(nt * (SB * SB / kReduceCnt / kReduceGroups)), 256, 0, st>>>(
-            sc.part.as<int32_t>(), nchunks, sc.tiles.as<int2>(), s->sp_nc.as<int32_t>(), s->sp_U, r0, r1, c0, c1,
+            sc.part.as<int32_t>(), sc.tinfo.as<int4>(), sc.tiles.as<int2>(), s->sp_nc.as<int32_t>(), s->sp_U, r0, r1,
+            c0, c1,
             upper ? 1 : 0, d_I, ldI,
             rare ? sc.rare_slab.as<uint32_t>() : nullptr, ep ? ep->D : nullptr, ep ? ep->ldD : 0,
             ep ? ep->off : nullptr, ep ? ep->empty_nan : 0, group_part(s));
