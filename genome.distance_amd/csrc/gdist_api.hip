@@ -16,6 +16,7 @@
 #include <new>
 
 #include "gdist_internal.hpp"
+#include "group_stats_host.hpp"
 
 namespace gdist {
 
@@ -1444,6 +1445,61 @@ int gdist_ctx_closest_timing(gdist_ctx* ctx, double* matrix_ms, double* select_m
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
         if (matrix_ms) *matrix_ms = ctx->closest_matrix_ms;
         if (select_ms) *select_ms = ctx->closest_select_ms;
+    });
+}
+
+// ---------------------------------------------------------------------------
+int gdist_group_stats(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, int64_t r1, int64_t c0, int64_t c1,
+                      int method, unsigned flags, int ntypes, const int32_t* labels, gdist_group_side* out,
+                      int64_t* bad) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_sets(sets);
+        GD_REQUIRE(sets->ctx == ctx, "sets belong to another context");
+        GD_REQUIRE(0 <= r0 && r0 <= r1 && r1 <= sets->nsets && 0 <= c0 && c0 <= c1 && c1 <= sets->nsets,
+                   "row/column range outside the set collection");
+        GD_REQUIRE(ntypes >= 1 && ntypes <= GDIST_GROUP_MAX_TYPES, "ntypes outside 1 .. GDIST_GROUP_MAX_TYPES");
+        GD_REQUIRE(labels && out && bad, "null labels or output");
+        GD_REQUIRE(!(flags & GDIST_OUT_DEVICE), "gdist_group_stats does not support GDIST_OUT_DEVICE");
+        const bool sketch = sets->kind == GDIST_SKETCH;
+        if (sketch) {
+            check_codes(sets);
+        } else {
+            GD_REQUIRE(method >= GDIST_METHOD_AUTO && method <= GDIST_METHOD_BITSET, "unknown method");
+            GD_REQUIRE(method != GDIST_METHOD_SORTED || sets->has_codes, "this collection holds bitsets only");
+        }
+        const int64_t nr = r1 - r0, nc = c1 - c0;
+        auto* s = const_cast<gdist_sets*>(sets);
+        int m = GDIST_METHOD_AUTO;
+        if (!sketch && nr > 0 && nc > 0) m = resolve_method(ctx, s, method, (double)nr * (double)nc);
+        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
+        ctx->last = Timing{};
+        // into locals first: a failure on the device leaves the outputs untouched too
+        std::vector<gdist_group_side> o((size_t)2 * ntypes);
+        std::vector<int64_t> b((size_t)ntypes);
+        gdist::group_stats(ctx, s, r0, r1, c0, c1, m, flags, ntypes, labels, o.data(), b.data());
+        std::copy(o.begin(), o.end(), out);
+        std::copy(b.begin(), b.end(), bad);
+    });
+}
+
+int gdist_group_stats_merge(gdist_group_side* acc, int64_t* bad_acc, const gdist_group_side* part,
+                            const int64_t* bad_part, int ntypes) {
+    return guard([&] {
+        GD_REQUIRE(acc && bad_acc && part && bad_part, "null argument");
+        GD_REQUIRE(ntypes >= 1 && ntypes <= GDIST_GROUP_MAX_TYPES, "ntypes outside 1 .. GDIST_GROUP_MAX_TYPES");
+        for (int i = 0; i < 2 * ntypes; i++) gdist::gstats::merge_side(acc + i, part + i);
+        for (int t = 0; t < ntypes; t++) bad_acc[t] += bad_part[t];
+    });
+}
+
+int gdist_ctx_group_stats_timing(gdist_ctx* ctx, double* matrix_ms, double* reduce_ms) {
+    return guard([&] {
+        GD_REQUIRE(ctx != nullptr, "null context");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        if (matrix_ms) *matrix_ms = ctx->group_matrix_ms;
+        if (reduce_ms) *reduce_ms = ctx->group_reduce_ms;
     });
 }
 

@@ -340,6 +340,8 @@ struct gdist_ctx {
     // the last gdist_closest call made with option time_kernels = 1: its
     // matrix kernels and its select kernel, ms over all steps (-1: not timed)
     double closest_matrix_ms = -1.0, closest_select_ms = -1.0;
+    // the same for the last gdist_group_stats call: matrix kernels, reduce kernel
+    double group_matrix_ms = -1.0, group_reduce_ms = -1.0;
     gdist_ctx() { for (auto& o : opt) o = gdist::kOptUnset; }
     int64_t option(gdist::Opt o, int64_t dflt) const { return opt[o] == gdist::kOptUnset ? dflt : opt[o]; }
     bool has_option(gdist::Opt o) const { return opt[o] != gdist::kOptUnset; }
@@ -706,6 +708,12 @@ void distance_epilogue(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t 
 void closest_blocks(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem, int64_t* rows, int64_t* cols);
 void closest(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
              unsigned flags, int n, double max_dist, int64_t* idx_out, double* d_out, int32_t* count_out);
+
+// group.hip — in-group / out-group distance summary (gdist_group_stats)
+// method: SORTED or BITSET (resolved by the caller); ignored for sketches.
+// labels: host, [ntypes][nsets]; out: [ntypes][2], bad: [ntypes], written whole
+void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
+                 unsigned flags, int ntypes, const int32_t* labels, gdist_group_side* out, int64_t* bad);
 
 // lsh.hip
 void lsh_build(gdist_ctx* ctx, const gdist_sets* sk, int stages, int buckets, uint64_t seed, gdist_lsh* L);

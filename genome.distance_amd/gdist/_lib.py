@@ -24,8 +24,16 @@ BITSET_KEEP_SINGLETONS = 0x1
 ALLGATHER_CONSUME = 0x1
 QUERY_ALL, QUERY_ANY_LE, QUERY_ARGMIN = 0, 1, 2
 CLOSEST_KEEP_SELF, CLOSEST_MAX_N = 0x1000, 512
+GROUP_MAX_TYPES = 8
 UNIQUE_ID_BYTES = 128
 OPTION_DEFAULT = -(1 << 63)   # GDIST_OPTION_DEFAULT
+
+
+class GroupSide(C.Structure):
+    """gdist_group_side: one side (in-group or out-group) of one grouping."""
+    _fields_ = [("n", C.c_int64), ("ones", C.c_int64), ("nans", C.c_int64),
+                ("min", C.c_double), ("max", C.c_double), ("mean", C.c_double), ("sdev", C.c_double),
+                ("sum", C.c_uint64 * 2), ("sumsq", C.c_uint64 * 3)]
 
 
 class GdistError(RuntimeError):
@@ -50,12 +58,12 @@ _REPO = os.path.dirname(_PKG)
 def tree_source_hash() -> str:
     """sha256 prefix of the library's sources in this tree, in the Makefile's
     order (csrc/*.hip by name, csrc/gdist_internal.hpp, csrc/sparse_bounds.hpp,
-    include/gdist.h)."""
+    csrc/group_stats_host.hpp, include/gdist.h)."""
     import glob
     import hashlib
     files = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hip")))
     files += [os.path.join(_PKG, "csrc", "gdist_internal.hpp"), os.path.join(_PKG, "csrc", "sparse_bounds.hpp"),
-              os.path.join(_REPO, "include", "gdist.h")]
+              os.path.join(_PKG, "csrc", "group_stats_host.hpp"), os.path.join(_REPO, "include", "gdist.h")]
     h = hashlib.sha256()
     for f in files:
         with open(f, "rb") as fh:
@@ -139,6 +147,9 @@ _SIGS = {
     "gdist_closest": (C.c_int, [_ctxp, _setp, _i64, _i64, _i64, _i64, C.c_int, _u32, C.c_int, _dbl, _i64p, _dblp,
                                 _i32p]),
     "gdist_ctx_closest_timing": (C.c_int, [_ctxp, _dblp, _dblp]),
+    "gdist_group_stats": (C.c_int, [_ctxp, _setp, _i64, _i64, _i64, _i64, C.c_int, _u32, C.c_int, _i32p, _vp, _i64p]),
+    "gdist_group_stats_merge": (C.c_int, [_vp, _i64p, _vp, _i64p, C.c_int]),
+    "gdist_ctx_group_stats_timing": (C.c_int, [_ctxp, _dblp, _dblp]),
     "gdist_comm_unique_id": (C.c_int, [C.c_char_p]),
     "gdist_comm_init": (C.c_int, [_ctxp, C.c_char_p, C.c_int, C.c_int]),
     "gdist_comm_init_host": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_void_p, _vp]),

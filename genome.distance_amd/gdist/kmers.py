@@ -126,6 +126,13 @@ class Context:
         L.check(L.lib.gdist_ctx_closest_timing(self.h, C.byref(m), C.byref(s)))
         return m.value, s.value
 
+    def group_stats_timing(self) -> tuple[float, float]:
+        """(matrix kernels ms, reduce kernel ms) of the last group_stats() call
+        made with option time_kernels = 1, summed over its steps (-1: not timed)."""
+        m, s = C.c_double(), C.c_double()
+        L.check(L.lib.gdist_ctx_group_stats_timing(self.h, C.byref(m), C.byref(s)))
+        return m.value, s.value
+
     def recent_timings(self, n: int) -> list[float]:
         """Kernel ms of the last n matrix calls, oldest first (waits for them)."""
         out = np.zeros(max(n, 1), dtype=np.float64)
@@ -275,6 +282,79 @@ def _as_bytes(s) -> bytes:
     return s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1")
 
 
+class GroupStats:
+    """Result of group_stats (gdist_group_stats): for each of T groupings the
+    in-group (column 0) and out-group (column 1) summary of the distances.
+
+    n, ones, nans: int64 [T, 2] (values below 1.0 summarised, distances equal
+    to 1.0, NaNs); min, max, mean, sdev: float64 [T, 2] (1.0 / 1.0 / 1.0 / 0.0
+    for a side with n == 0); bad: int64 [T] pairs with an unlabelled set;
+    sum, sumsq: [T][2] Python ints, the exact sums of m = d * 2^53 and m * m.
+    `sides` / `bad_raw` are the C arrays (gdist_group_side [2 T], int64 [T])."""
+
+    def __init__(self, sides, bad):
+        self.sides, self.bad_raw = sides, bad
+        T = len(bad)
+        self.ntypes = T
+
+        def arr(name, dtype):
+            return np.array([[getattr(sides[2 * t + k], name) for k in range(2)] for t in range(T)], dtype=dtype)
+        self.n, self.ones, self.nans = arr("n", np.int64), arr("ones", np.int64), arr("nans", np.int64)
+        self.min, self.max = arr("min", np.float64), arr("max", np.float64)
+        self.mean, self.sdev = arr("mean", np.float64), arr("sdev", np.float64)
+        self.bad = np.array(list(bad), dtype=np.int64)
+
+        def limbs(v):
+            return sum(int(x) << (64 * i) for i, x in enumerate(v))
+        self.sum = [[limbs(sides[2 * t + k].sum) for k in range(2)] for t in range(T)]
+        self.sumsq = [[limbs(sides[2 * t + k].sumsq) for k in range(2)] for t in range(T)]
+
+    @classmethod
+    def empty(cls, ntypes: int) -> "GroupStats":
+        """No pair yet: every side in its n == 0 form (the identity of merge)."""
+        sides = (L.GroupSide * (2 * ntypes))()
+        for s in sides:
+            s.min = s.max = s.mean = 1.0
+        return cls(sides, (C.c_int64 * ntypes)())
+
+    def tobytes(self) -> bytes:
+        """The struct array and the bad counts as the library wrote them."""
+        return bytes(self.sides) + bytes(self.bad_raw)
+
+    @classmethod
+    def frombytes(cls, data: bytes) -> "GroupStats":
+        """The summary tobytes() wrote (another rank's, received as bytes)."""
+        per = 2 * C.sizeof(L.GroupSide) + 8
+        T = len(data) // per
+        if T < 1 or T * per != len(data):
+            raise ValueError(f"{len(data)} bytes are not a whole number of groupings ({per} bytes each)")
+        sides = (L.GroupSide * (2 * T)).from_buffer_copy(data[:T * (per - 8)])
+        return cls(sides, (C.c_int64 * T).from_buffer_copy(data[T * (per - 8):]))
+
+    def merge(self, other: "GroupStats") -> "GroupStats":
+        """This summary and `other`'s (disjoint pairs, the same groupings) as
+        one, exactly (gdist_group_stats_merge): the ranks of a row-sharded run
+        merge to the bytes of a single call."""
+        if other.ntypes != self.ntypes:
+            raise ValueError("summaries of different groupings")
+        T = self.ntypes
+        sides, bad = (L.GroupSide * (2 * T))(), (C.c_int64 * T)()
+        C.memmove(sides, self.sides, C.sizeof(sides))
+        C.memmove(bad, self.bad_raw, C.sizeof(bad))
+        L.check(L.lib.gdist_group_stats_merge(C.addressof(sides), bad, C.addressof(other.sides), other.bad_raw, T))
+        return GroupStats(sides, bad)
+
+    @property
+    def low(self) -> np.ndarray:
+        """mean - sdev, fp64 (DistanceCheckProcessor.java:216-217)."""
+        return self.mean - self.sdev
+
+    @property
+    def high(self) -> np.ndarray:
+        """mean + sdev, fp64 (DistanceCheckProcessor.java:216,218)."""
+        return self.mean + self.sdev
+
+
 class _Handle:
     def __init__(self, ctx: Context, h: C.c_void_p):
         self.ctx, self.h = ctx, h
@@ -316,6 +396,25 @@ class _Handle:
         L.check(L.lib.gdist_closest(self.ctx.h, self.h, r0, r1, c0, c1, method, fl, int(n), float(max_dist),
                                     L.ptr(bi, C.c_int64), L.ptr(bd, C.c_double), L.ptr(bc, C.c_int32)))
         return idx, d, cnt
+
+    def _group_stats(self, labels, rows, cols, upper: bool, method: int, flags: int) -> GroupStats:
+        ns = len(self)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.ndim == 1:
+            lab = lab[None, :]
+        if lab.ndim != 2 or lab.shape[1] != ns:
+            raise ValueError(f"labels must be [T, {ns}] or [{ns}], not {list(lab.shape)}")
+        T = lab.shape[0]
+        if not 1 <= T <= L.GROUP_MAX_TYPES:
+            raise ValueError(f"{T} groupings: 1 .. {L.GROUP_MAX_TYPES} a call")
+        r0, r1 = rows or (0, ns)
+        c0, c1 = cols or (0, ns)
+        sides, bad = (L.GroupSide * (2 * T))(), (C.c_int64 * T)()
+        buf = lab if lab.size else np.zeros(1, dtype=np.int32)
+        fl = flags | (L.UPPER_TRIANGLE if upper else 0)
+        L.check(L.lib.gdist_group_stats(self.ctx.h, self.h, r0, r1, c0, c1, method, fl, T, L.ptr(buf, C.c_int32),
+                                        C.addressof(sides), bad))
+        return GroupStats(sides, bad)
 
     def getClosest(self, n: int, max_dist: float, **kw) -> list[list[tuple[int, float]]]:
         """getClosest(kmers, n, maxDist) for every row of closest(n, max_dist, **kw)
@@ -607,6 +706,16 @@ class KmerSets(_Handle):
         -1 / 1.0. d is bit-identical to matrix()'s D; the N x N stays on the device."""
         return self._closest(n, max_dist, rows, cols, method, flags, keep_self)
 
+    def group_stats(self, labels, rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,
+                    upper: bool = True, method: int = L.METHOD_AUTO, flags: int = 0) -> GroupStats:
+        """In-group / out-group summary of the distances of rows x cols
+        (gdist_group_stats; GroupTypeSpec.java:77-95): labels int32 [T, N] or
+        [N], the group of every set under each grouping (< 0: none, the pair
+        is counted as bad). upper: only the pairs j > i. The distances are
+        matrix()'s D bit for bit and never leave the device; the sums are
+        exact, so the result does not depend on method or block sizes."""
+        return self._group_stats(labels, rows, cols, upper, method, flags)
+
     def row_query(self, q: int, cols: Iterable[int], mode: int = L.QUERY_ALL, t: float = 1.0):
         cl = np.ascontiguousarray(np.fromiter(cols, dtype=np.int64))
         D = np.zeros(max(len(cl), 1), dtype=np.float64)
@@ -710,6 +819,12 @@ class SketchSets(_Handle):
         SKETCH_JACCARD, EMPTY_NAN): the same result shape as KmerSets.closest, d
         bit-identical to matrix()'s D."""
         return self._closest(n, max_dist, rows, cols, L.METHOD_AUTO, flags, keep_self)
+
+    def group_stats(self, labels, rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,
+                    upper: bool = True, method: int = L.METHOD_AUTO, flags: int = 0) -> GroupStats:
+        """In-group / out-group summary of the sketch distances (gdist_group_stats;
+        flags: SKETCH_JACCARD, EMPTY_NAN; method is ignored): as KmerSets.group_stats."""
+        return self._group_stats(labels, rows, cols, upper, L.METHOD_AUTO, flags)
 
     def matrix_device(self, d_common: int | None, d_D: int | None, ld: int, rows, cols, upper=False, flags=0):
         fl = flags | L.OUT_DEVICE | (L.UPPER_TRIANGLE if upper else 0)

@@ -9,6 +9,7 @@ row-block / row-query calls on the device:
   fasta_reps       FastaDistanceRepsProcessor (fastaReps) FastaDistanceRepsProcessor.java:58-149
   distance_reps    DistanceRepsProcessor   (distReps)   DistanceRepsProcessor.java:140-275
   width_processor  WidthProcessor          (width)      WidthProcessor.java:88-208
+  distance_check   DistanceCheckProcessor  (distCheck)  DistanceCheckProcessor.java:149-223
 
 Output rows are emitted in (row, column) order; the reference's fastaDist
 order is nondeterministic (rows run in parallel, FastaDistanceProcessor.java:157,188),
@@ -365,3 +366,59 @@ def closest_genomes(queries: Sequence[Genome], subjects: Sequence[Genome], out: 
             out.write(f"{s.id}\t{s.name}\t{q.id}\t{q.name}\t{java_format_f(float(d[a, r]), 8, 3)}\n")
             found += 1
     return nq, found, none
+
+
+def group_labels(ids: Sequence[str], groupings: dict) -> tuple[list[str], np.ndarray]:
+    """(type names, int32 labels [T, N]) of `groupings` (type name -> {genome id
+    -> group id}) for the sets `ids`: group ids become integers by first
+    appearance along `ids`, a genome the grouping does not hold becomes -1
+    (the null group of GroupTypeSpec.java:78-80)."""
+    names = list(groupings)
+    lab = np.full((len(names), len(ids)), -1, dtype=np.int32)
+    for t, name in enumerate(names):
+        gmap, seen = groupings[name], {}
+        for i, gid in enumerate(ids):
+            grp = gmap.get(gid)
+            if grp is not None:
+                lab[t, i] = seen.setdefault(grp, len(seen))
+    return names, lab
+
+
+def write_distance_check(stats, names: Sequence[str], out: TextIO, name: str, header: bool = True) -> int:
+    """The distCheck table of one distance source `name` from a GroupStats: an
+    `in` and an `out` row per grouping (DistanceCheckProcessor.java:180-181),
+    doubles as Java prints them, `ones` an int. A side without a value below
+    1.0 prints 1.0 five times (DistanceCheckProcessor.java:203-209); low and
+    high are mean -/+ sdev in fp64 (DistanceCheckProcessor.java:216-218).
+    Returns the bad pairs over all groupings (DistanceCheckProcessor.java:185)."""
+    if header:
+        # the header of DistanceCheckProcessor.java:151
+        out.write("dist_file\tgroup_type\tin_out\tmin\tlow\tmean\thigh\tmax\tones\n")
+    low, high = stats.low, stats.high
+    for t, gtype in enumerate(names):
+        for k, side in enumerate(("in", "out")):
+            if stats.n[t, k] == 0:
+                vals = [1.0] * 5
+            else:
+                vals = [stats.min[t, k], low[t, k], stats.mean[t, k], high[t, k], stats.max[t, k]]
+            # the row of DistanceCheckProcessor.java:221-222
+            cells = [name, gtype, side] + [java_double(float(v)) for v in vals] + [str(int(stats.ones[t, k]))]
+            out.write("\t".join(cells) + "\n")
+    return int(stats.bad.sum())
+
+
+def distance_check(sets, ids: Sequence[str], groupings: dict, out: TextIO, name: str, header: bool = True,
+                   **kw) -> int:
+    """distCheck (DistanceCheckProcessor.java:149-223) over the distances of a
+    device-resident collection instead of a distance file: which grouping the
+    distance predicts best. `sets` is a KmerSets or SketchSets whose set i is
+    genome ids[i]; `groupings` maps a type name to {genome id -> group id};
+    **kw goes to group_stats (rows, cols, upper, method, flags; by default the
+    pairs j > i, each pair once as a distance file lists them). min, max, ones
+    and the counts equal the reference's on the same pairs; its mean and sd
+    come from an incremental update in file order and may differ from these
+    exactly rounded ones in the last digits. Returns the bad pairs."""
+    if len(ids) != len(sets):
+        raise ValueError(f"{len(ids)} ids for {len(sets)} sets")
+    names, lab = group_labels(ids, groupings)
+    return write_distance_check(sets.group_stats(lab, **kw), names, out, name, header)

@@ -27,6 +27,8 @@
  *   gdist_closest          getClosest(kmers, n, maxDist), exhaustively
  *                          (every column, no LSH buckets)        MashProcessor.java:150, FindProcessor.java:110
  *                          --maxDist of the genomes table        GenomeProcessor.java:58-60,89
+ *   gdist_group_stats      recordDistance over a distance table  GroupTypeSpec.java:77-95
+ *                          in / out-group min, mean, sd, max     DistanceCheckProcessor.java:200-223
  *   gdist_sets_allgather   (new) RCCL all-gather of packed sets for row-sharded N×N
  *
  * Kmer code spec (shared by the device packer, the CPU oracle in oracle/ and
@@ -392,6 +394,60 @@ int  gdist_closest(gdist_ctx* ctx, const gdist_sets* sets,
  * kernels (intersect or sketch) and the select kernel apart; -1 when the
  * call was not timed. */
 int  gdist_ctx_closest_timing(gdist_ctx* ctx, double* matrix_ms, double* select_ms);
+
+/* ---- in-group / out-group distance summary ----------------------------- */
+/* The distCheck report (DistanceCheckProcessor.java:149-223) over the pairs
+ * of a rectangle without the distance table leaving the device: for each of
+ * ntypes groupings of the sets (labels[t * nsets + i] the group of set i
+ * under grouping t, < 0: the set has none) the pairs (i, j), i in [r0, r1),
+ * j in [c0, c1), are split as GroupTypeSpec.java:77-95 splits them. With
+ * GDIST_UPPER_TRIANGLE only j > i counts; without it a diagonal pair inside
+ * the rectangle counts like any other. A label < 0 on either set adds 1 to
+ * bad[t] and nothing else (GroupTypeSpec.java:80-81); otherwise the pair
+ * goes to out[2 t] (equal labels: in-group) or out[2 t + 1] (out-group).
+ * d is the bit pattern gdist_intersect_matrix (kmer sets; method AUTO /
+ * SORTED / BITSET resolved as gdist_closest resolves it) or
+ * gdist_sketch_matrix (GDIST_SKETCH collections: method ignored) writes with
+ * the same flags (GDIST_EMPTY_NAN, GDIST_SKETCH_JACCARD). Within a side
+ * d == 1.0 adds to ones (GroupTypeSpec.java:84-87), NaN to nans, any other d
+ * to n, min, max, sum and sumsq. Java's addValue(NaN) would poison the
+ * statistics; this call counts NaNs apart instead.
+ *
+ * Every d < 1.0 the library produces is an integer multiple of 2^-53, so
+ * sum and sumsq are exact integers of m = d * 2^53 and the result does not
+ * depend on block sizes, method, run or rank: gdist_group_stats_merge adds
+ * the results of disjoint rectangles (the ranks of a row-sharded run) to the
+ * bytes one call over their union returns. mean and sdev (bias-corrected,
+ * SummaryStatistics.getStandardDeviation) come from the exact sums, within
+ * 1 / 2 ulp of the exact values; the reference's incremental update in file
+ * order may differ from them in the last digits.
+ *
+ * The walk is gdist_closest's (options "closest_rows" / "closest_cols"). An
+ * empty range: GDIST_OK, every side in its n == 0 form, bad 0. EINVAL (the
+ * outputs stay untouched): a bad range, ntypes outside 1..GDIST_GROUP_MAX_TYPES,
+ * a null pointer, GDIST_OUT_DEVICE, SORTED on a bitsets-only collection. */
+#define GDIST_GROUP_MAX_TYPES 8
+typedef struct {
+    int64_t  n, ones, nans;     /* d < 1.0 values summarised; d == 1.0; NaN (GDIST_EMPTY_NAN only) */
+    double   min, max;          /* over the n values; 1.0 / 1.0 when n == 0 */
+    double   mean, sdev;        /* from the exact sums; 1.0 / 0.0 when n == 0; sdev 0.0 when n == 1 */
+    uint64_t sum[2];            /* sum of m = d * 2^53, little-endian limbs */
+    uint64_t sumsq[3];          /* sum of m * m */
+} gdist_group_side;
+int  gdist_group_stats(gdist_ctx* ctx, const gdist_sets* sets,
+                       int64_t r0, int64_t r1, int64_t c0, int64_t c1,
+                       int method, unsigned flags, int ntypes,
+                       const int32_t* labels /* [ntypes][nsets], host */,
+                       gdist_group_side* out /* [ntypes][2]: in, out */, int64_t* bad /* [ntypes] */);
+/* acc += part for every side and bad count (host only, exact): integer fields
+ * limb-wise with carries, min / max over the sides holding values, mean and
+ * sdev recomputed. EINVAL: a null pointer, ntypes outside 1..GDIST_GROUP_MAX_TYPES. */
+int  gdist_group_stats_merge(gdist_group_side* acc, int64_t* bad_acc, const gdist_group_side* part,
+                             const int64_t* bad_part, int ntypes);
+/* HIP-event time (ms, summed over the steps) of the last gdist_group_stats
+ * call made with option "time_kernels" = 1: the matrix kernels and the reduce
+ * kernel apart; -1 when the call was not timed. */
+int  gdist_ctx_group_stats_timing(gdist_ctx* ctx, double* matrix_ms, double* reduce_ms);
 
 /* ---- multi-GPU (RCCL over xGMI) -------------------------------------- */
 #define GDIST_UNIQUE_ID_BYTES 128
