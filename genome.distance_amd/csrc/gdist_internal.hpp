@@ -204,6 +204,8 @@ struct Timing {
     X(SPARSE_WG_PER_CU, "sparse_wg_per_cu")   /* chunking target of the sparse tiles (default 4) */            \
     X(SPARSE_SUN, "sparse_sun")               /* slots per lane in flight: 2 / 3 / 4 (default 4) */            \
     X(SPARSE_DYN, "sparse_dyn")               /* 1 (default): a tile workgroup's waves claim word batches in turn; 0: equal runs */ \
+    X(SPARSE_BATCH, "sparse_batch")           /* words a batch of a tile workgroup's waves: 0 (default) 48, and a chunk of at most 8 x 48 words in equal shares over the 8 waves; 1..48 fixed (48: rounds 4-7) */ \
+    X(SPARSE_WTAIL, "sparse_wtail")           /* 1 (default): a walk window's leftover groups two to a step; 0: one at a time */ \
     X(SPARSE_DIAG22, "sparse_diag22")         /* 1 (default): diagonal tiles in 2 x 2 micro-tiles too (sparse_mt 2) */ \
     X(SPARSE_RPART22, "sparse_rpart22")       /* 1 (default): row-trimmed sparse tiles in 2 x 2 micro-tiles too */ \
     X(SPARSE_MT, "sparse_mt")                 /* off-diagonal micro-tiles: 1 (1 x 2) / 2 (2 x 2, default) */   \

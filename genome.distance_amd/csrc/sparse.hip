@@ -801,13 +801,26 @@ __device__ __forceinline__ void sparse_diag22_slots(const int4* __restrict__ rec
     }
 }
 
+// one step of SU groups of 64 slots from slot fb, in the walk's mode
+template <int SU, int MODE>
+__device__ __forceinline__ void sparse_step(const int4* __restrict__ rec, const unsigned long long* __restrict__ masks,
+                                            int W0, int last, int fb, int lane, const SparseWalk& e,
+                                            uint32_t* __restrict__ cnt, bool mirror) {
+    if (MODE == 0) sparse_diag_slots<SU>(rec, masks, W0, last, fb, lane, e, cnt, mirror);
+    else if (MODE == 1) sparse_off_slots<SU>(rec, masks, W0, last, fb, lane, e, cnt);
+    else if (MODE == 2) sparse_off22_slots<SU>(rec, masks, W0, last, fb, lane, e, cnt);
+    else sparse_diag22_slots<SU>(rec, masks, W0, last, fb, lane, e, cnt, mirror);
+}
+
 // A batch's walk: windows of G groups of 64 slots (G a multiple of SUN):
 // the window's last-slot masks, then SUN groups per step while whole steps
-// remain, one group at a time after
+// remain. The groups left over (fewer than SUN, the last one partial) go two
+// to a step while two remain (wtail, option sparse_wtail; only the last group
+// of a walk holds slots past `total`, as before), one group at a time after.
 template <int SUN, int MODE>
 __device__ __forceinline__ void sparse_walk(const int4* __restrict__ rec, unsigned long long* __restrict__ masks,
                                             int last, int total, int lane, const SparseWalk& e,
-                                            uint32_t* __restrict__ cnt, bool mirror) {
+                                            uint32_t* __restrict__ cnt, bool mirror, bool wtail) {
     constexpr int G = kWinGroups / SUN * SUN;
     for (int W0 = 0; W0 < total; W0 += 64 * G) {
         if (lane < G) masks[lane] = 0ull;
@@ -819,18 +832,13 @@ __device__ __forceinline__ void sparse_walk(const int4* __restrict__ rec, unsign
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
         const int wend = total < W0 + 64 * G ? total : W0 + 64 * G;
         int fb = W0;
-        for (; fb + 64 * SUN <= wend; fb += 64 * SUN) {
-            if (MODE == 0) sparse_diag_slots<SUN>(rec, masks, W0, last, fb, lane, e, cnt, mirror);
-            else if (MODE == 1) sparse_off_slots<SUN>(rec, masks, W0, last, fb, lane, e, cnt);
-            else if (MODE == 2) sparse_off22_slots<SUN>(rec, masks, W0, last, fb, lane, e, cnt);
-            else sparse_diag22_slots<SUN>(rec, masks, W0, last, fb, lane, e, cnt, mirror);
-        }
-        for (; fb < wend; fb += 64) {
-            if (MODE == 0) sparse_diag_slots<1>(rec, masks, W0, last, fb, lane, e, cnt, mirror);
-            else if (MODE == 1) sparse_off_slots<1>(rec, masks, W0, last, fb, lane, e, cnt);
-            else if (MODE == 2) sparse_off22_slots<1>(rec, masks, W0, last, fb, lane, e, cnt);
-            else sparse_diag22_slots<1>(rec, masks, W0, last, fb, lane, e, cnt, mirror);
-        }
+        for (; fb + 64 * SUN <= wend; fb += 64 * SUN)
+            sparse_step<SUN, MODE>(rec, masks, W0, last, fb, lane, e, cnt, mirror);
+        if (SUN > 2 && wtail)
+            for (; fb + 64 < wend; fb += 64 * 2)
+                sparse_step<2, MODE>(rec, masks, W0, last, fb, lane, e, cnt, mirror);
+        for (; fb < wend; fb += 64)
+            sparse_step<1, MODE>(rec, masks, W0, last, fb, lane, e, cnt, mirror);
         __builtin_amdgcn_wave_barrier();
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
     }
@@ -848,12 +856,14 @@ struct TileWalk {
     int rlo, rhi;
     bool rpart, diag, mirror, r22;
     bool d22;                             // diagonal tiles in 2 x 2 micro-tiles (MT 2, option sparse_diag22)
+    bool wtail;                           // a window's leftover groups two to a step (option sparse_wtail)
 };
 
-// One batch of up to kBatchWords words [s0, we) walked over global memory
-// (only >= 0: that lane's word alone)
+// One batch of words [s0, be), be - s0 <= kBatchWords (lane l takes word
+// s0 + l: the lanes from the batch's size on hold no word), walked over
+// global memory (only >= 0: that lane's word alone)
 template <int SUN, int MT>
-__device__ __forceinline__ void global_batch(const TileWalk& tc, int64_t s0, int64_t we, int only, int lane,
+__device__ __forceinline__ void global_batch(const TileWalk& tc, int64_t s0, int64_t be, int only, int lane,
                                              int4* __restrict__ wrec, unsigned long long* __restrict__ masks,
                                              uint32_t* __restrict__ cnt) {
     const int64_t* offA = tc.offA;
@@ -865,10 +875,11 @@ __device__ __forceinline__ void global_batch(const TileWalk& tc, int64_t s0, int
     const int rlo = tc.rlo, rhi = tc.rhi;
     const bool rpart = tc.rpart, diag = tc.diag, mirror = tc.mirror, r22 = tc.r22;
     const bool d22 = MT == 2 && tc.d22;
+    const bool wtail = tc.wtail;
     const int64_t s = s0 + lane;
     int64_t rb = ra0, cb = cb0;
     int nr = 0, ncl = 0;
-    if (lane < kBatchWords && s < we && (only < 0 || lane == only)) {
+    if (lane < kBatchWords && s < be && (only < 0 || lane == only)) {
         rb = offA[s]; nr = (int)(offA[s + 1] - rb);
         cb = offB[s]; ncl = (int)(offB[s + 1] - cb);
         if (rpart) {                               // lists are sorted by set: trim both ends
@@ -914,10 +925,10 @@ __device__ __forceinline__ void global_batch(const TileWalk& tc, int64_t s0, int
     const int last = P > 0 ? incl - 1 : 0x7FFFFFFF;
     __builtin_amdgcn_wave_barrier();
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
-    if (MT == 2 && diag && d22) sparse_walk<2, 3>(wrec, masks, last, total, lane, e, cnt, mirror);
-    else if (diag) sparse_walk<SUN, 0>(wrec, masks, last, total, lane, e, cnt, mirror);
-    else if (MT == 2 && r22) sparse_walk<MT == 2 ? SUN : 1, 2>(wrec, masks, last, total, lane, e, cnt, false);
-    else sparse_walk<SUN, 1>(wrec, masks, last, total, lane, e, cnt, false);
+    if (MT == 2 && diag && d22) sparse_walk<2, 3>(wrec, masks, last, total, lane, e, cnt, mirror, wtail);
+    else if (diag) sparse_walk<SUN, 0>(wrec, masks, last, total, lane, e, cnt, mirror, wtail);
+    else if (MT == 2 && r22) sparse_walk<MT == 2 ? SUN : 1, 2>(wrec, masks, last, total, lane, e, cnt, false, wtail);
+    else sparse_walk<SUN, 1>(wrec, masks, last, total, lane, e, cnt, false, wtail);
 }
 
 template <int SUN, int MT>
@@ -927,17 +938,19 @@ __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
     const int2* __restrict__ wgmap, int nchunks, int64_t r0, int64_t r1,
     int64_t c0, int64_t c1, int upper, int32_t* __restrict__ I, int64_t ldI, int32_t* __restrict__ part, int64_t Wdp,
     int64_t N, const unsigned long long* __restrict__ slab_bits, int slabs, GroupPart gp, int xmap, int ntiles,
-    RareSlab rs, int dyn, int diag22, int rpart22) {
+    RareSlab rs, int dyn, int diag22, int rpart22, int batch, int wtail) {
     // gp: the group tier's part of every pair, added with the constant part
     // slab_bits / slabs: the in-kernel fold's dense words (set-major [N][Wdp])
-    __shared__ uint32_t cnt[SB * SB / 2];                  // 32 KiB, 16-bit counters (cnt_index layout)
+    __shared__ __attribute__((aligned(16))) uint32_t cnt[SB * SB / 2];   // 32 KiB, 16-bit counters (cnt_index layout)
     __shared__ int4 rec[SNW][64];                          // 8 KiB: the batch's walk records
     // dyn: the chunk's next unclaimed batch, in wave 0's unused last record
     // (an LDS variable of its own would take the workgroup past 40 KiB: 3
     // workgroups a CU instead of 4, and the compiler then spends 80 VGPRs)
     int& next_batch = rec[0][63].w;
     // the rare rows of this step (above) are the launch's LAST workgroups:
-    // they fill the CUs the tile workgroups' last round leaves idle
+    // they fill the CUs the tile workgroups' last round leaves idle (ahead of
+    // the lightest eighth of the tile workgroups they delay those by a round
+    // of their own: C2 0.1057 ms a step against 0.0989, profiles/r08/ab_c2.txt)
     const unsigned ntw = gridDim.x - (unsigned)rs.nrare;
     if (blockIdx.x >= ntw) {
         rare_slab_row(rs, (int)(blockIdx.x - ntw), r0, c0, c1, upper, cnt);
@@ -980,7 +993,12 @@ __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
     // trimmed list's odd last pair reads the entry after the range as its
     // second row — a row outside the region, whose counters no store reads
     const bool r22 = MT == 2 && !diag && (!rpart || rpart22);
-    for (int t = threadIdx.x; t < SB * SB / 2; t += SNT) cnt[t] = 0;
+    // 16 bytes a thread, four stores at constant offsets from one address
+    // (as a loop over t the same stores cost <3, 2> a spilled VGPR)
+    static_assert(SB * SB / 8 % SNT == 0, "whole 16-byte stores per thread");
+#pragma unroll
+    for (int t = 0; t < SB * SB / 8 / SNT; t++)
+        reinterpret_cast<uint4*>(cnt)[t * SNT + threadIdx.x] = make_uint4(0, 0, 0, 0);
     if (threadIdx.x == 0) next_batch = SNW;
     __syncthreads();
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -992,24 +1010,37 @@ __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
     const uint32_t zA = (uint32_t)(ntot - ra0), zB = (uint32_t)(ntot - cb0);
     const TileWalk tc{offA, offB, ent, ra0, cb0, zA, zB,
                       SparseWalk{reinterpret_cast<const char*>(ent + ra0), reinterpret_cast<const char*>(ent + cb0)},
-                      rlo, rhi, rpart, diag, mirror, r22, diag22 != 0};
+                      rlo, rhi, rpart, diag, mirror, r22, diag22 != 0, wtail != 0};
     int4* wrec = &rec[wv][0];
     unsigned long long* masks = reinterpret_cast<unsigned long long*>(&rec[wv][kBatchWords + 1]);
-    // the wave's share of the chunk's words, in batches of kBatchWords: an
-    // equal run of words per wave, or (dyn, default) batch wv first and then
-    // the next unclaimed one (an LDS counter), so that a wave that drew light
-    // words takes more of them instead of idling until the heaviest wave ends
+    // The batch size bw, one for the whole chunk (option sparse_batch 1..48
+    // fixes it; 48 is the batch of rounds 4-7). A chunk of at most SNW * 48
+    // words is one batch a wave at the most, and the workgroup lasts as long
+    // as its longest batch whatever the other waves do: its n words are
+    // dealt in equal shares over the 8 waves (a 219-word chunk is 8 batches
+    // of 28 words, not 4 of 48 and one of 27 with three waves idle). Longer
+    // chunks keep 48: the claims already level their waves, and equal shares
+    // over ceil(n / (SNW * 48)) rounds only add batches, each with its fixed
+    // cost (C2: 0.0989 ms a step against 0.0986, and 0.0959 with one-round
+    // chunks alone in equal shares; profiles/r08/ab_c2.txt).
+    const int n = (int)(se - sb);
+    int bw = batch > 0 ? batch : n <= SNW * kBatchWords ? (n + SNW - 1) / SNW : kBatchWords;
+    bw = bw < 1 ? 1 : bw > kBatchWords ? kBatchWords : bw;
+    // the wave's share of the chunk's words, in batches of bw: an equal run
+    // of words per wave, or (dyn, default) batch wv first and then the next
+    // unclaimed one (an LDS counter), so that a wave that drew light words
+    // takes more of them instead of idling until the heaviest wave ends
     const int64_t per = ceil_div(se - sb, (int64_t)SNW);
-    const int64_t wb = dyn ? sb + (int64_t)wv * kBatchWords : sb + (int64_t)wv * per;
+    const int64_t wb = dyn ? sb + (int64_t)wv * bw : sb + (int64_t)wv * per;
     const int64_t we = dyn ? se : (wb + per < se ? wb + per : se);
     for (int64_t s0 = wb; s0 < we;) {
-        global_batch<SUN, MT>(tc, s0, we, -1, lane, wrec, masks, cnt);
+        global_batch<SUN, MT>(tc, s0, s0 + bw < we ? s0 + bw : we, -1, lane, wrec, masks, cnt);
         if (dyn) {
             int nb = 0;
             if (lane == 0) nb = atomicAdd(&next_batch, 1);
-            s0 = sb + (int64_t)__builtin_amdgcn_readfirstlane(__shfl(nb, 0, 64)) * kBatchWords;
+            s0 = sb + (int64_t)__builtin_amdgcn_readfirstlane(__shfl(nb, 0, 64)) * bw;
         } else {
-            s0 += kBatchWords;
+            s0 += bw;
         }
     }
     if (ch < slabs) {
@@ -1046,7 +1077,8 @@ __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
     __syncthreads();
     if (part) {
         uint32_t* dst = reinterpret_cast<uint32_t*>(part) + ((int64_t)ti.z + ch) * (SB * SB / 2);
-        for (int t = threadIdx.x; t < SB * SB / 2; t += SNT) dst[t] = cnt[t];
+        for (int t = threadIdx.x; t < SB * SB / 8; t += SNT)
+            reinterpret_cast<uint4*>(dst)[t] = reinterpret_cast<const uint4*>(cnt)[t];
         return;
     }
     for (int t = threadIdx.x; t < SB * SB; t += SNT) {
@@ -1692,6 +1724,15 @@ void sparse_plan(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, in
             // tapered: 40 / 44 / 48 / 56 / 62 chunks ran 0.120 / 0.114 /
             // 0.099-0.108 / 0.102 / 0.102 ms a step: under 1.7 rounds the
             // first workgroups are the launch's critical path, so 2 (57).
+            // Round 8, the one-round chunks' words in equal shares over the
+            // waves and 3/4 as many chunks on the diagonal: 44 / 48 / 50 /
+            // 52 / 57 / 62 chunks ran 0.0959 / 0.0953 / 0.0954 / 0.0956 /
+            // 0.0958 / 0.0972 ms (rounds within 0.0003; taper 0.6 at 48 /
+            // 52 / 57: 0.0987 / 0.0995 / 0.0976, taper 0.9: 0.0958 / 0.0952
+            // / 0.0959), C2-realistic 0.284-0.287 at every count: 48-52 gain
+            // 0.0002-0.0005 on C2, less than two spreads and towards that
+            // cliff, so the count and the taper stay
+            // (profiles/r08/ab_c2.txt).
             if (bal >= 2)
                 n0 = std::max<int64_t>(std::max<int64_t>((n0 + 1) / 2, s->sp_fold_slabs),
                                        std::min<int64_t>(n0, ceil_div(2 * target, sc.ntiles)));
@@ -1878,6 +1919,8 @@ bool sparse_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
     const int sun = (int)ctx->option(OPT_SPARSE_SUN, mt == 2 ? 3 : 4);
     GD_REQUIRE(sun >= 2 && sun <= 4, "sparse_sun: 2, 3 or 4");
     GD_REQUIRE(mt == 1 || mt == 2, "sparse_mt: 1 (1 x 2 micro-tiles) or 2 (2 x 2)");
+    const int batch = (int)ctx->option(OPT_SPARSE_BATCH, 0);
+    GD_REQUIRE(batch >= 0 && batch <= kBatchWords, "sparse_batch: 0 (by the chunk) or 1..48 words");
     auto kern = mt == 2 ? (sun == 2 ? sparse_tile_kernel<2, 2> : sun == 4 ? sparse_tile_kernel<4, 2> : sparse_tile_kernel<3, 2>)
                         : (sun == 2 ? sparse_tile_kernel<2, 1> : sun == 4 ? sparse_tile_kernel<4, 1> : sparse_tile_kernel<3, 1>);
     // the rare tier's pairs of this step: the launch's trailing workgroups
@@ -1905,7 +1948,8 @@ bool sparse_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
                                          s->Wd, s->nsets, s->dbits.as<unsigned long long>(), s->sp_fold_slabs,
                                          group_part(s), xmap ? 1 : 0, (int)nt, rs,
                                          (int)ctx->option(OPT_SPARSE_DYN, 1), (int)ctx->option(OPT_SPARSE_DIAG22, 1),
-                                         (int)ctx->option(OPT_SPARSE_RPART22, 1));
+                                         (int)ctx->option(OPT_SPARSE_RPART22, 1), batch,
+                                         (int)ctx->option(OPT_SPARSE_WTAIL, 1));
     GD_HIP(hipGetLastError());
     ft.end();
     if (sc.use_part) {
