@@ -186,7 +186,8 @@ struct Timing {
 // (MethodTableProcessor.java:275, concurrent getDistance) share its options.
 // Every option preserves results: each only picks among exact kernels,
 // tilings, thresholds or setup paths, and the parity tests run each non-default
-// value against the oracle (tests/test_gpu_parity.py, test_gpu_options.py).
+// value against the oracle (tests/option_cases.py names the test for every
+// option; tests/test_option_table.py fails when one is added without an entry).
 #define GDIST_OPTIONS(X)                                                                                       \
     X(TRACE, "trace")                         /* 1: setup stage timings and plans on stderr */                 \
     X(RARE_T, "rare_t")                       /* rare-tier threshold T (default: histogram cost model) */      \

@@ -144,6 +144,17 @@ def run_case(name, c, ctx, rank, world):
             assert gs.variant_info()[0] == 0 and gs.rare_info()[1] > 0, (rank, gs.rare_info())
             assert gs.build_timing()["shares"] == world
             results[leg] = gs.matrix((r0, r1), (0, n), upper=True, method=gdist.METHOD_BITSET)
+            # option split_build = 0: every rank builds all of the gathered
+            # collection by itself (one share, no collective); the same rows
+            # bit for bit (the parent checks the split build's against the oracle)
+            ctx.set_option("split_build", 0)
+            gs.build_bitsets()
+            assert gs.variant_info()[0] == 0 and gs.rare_info()[1] > 0, (rank, gs.rare_info())
+            assert gs.build_timing()["shares"] == 1, (rank, gs.build_timing())
+            I0, D0 = gs.matrix((r0, r1), (0, n), upper=True, method=gdist.METHOD_BITSET)
+            ctx.set_option("split_build", None)
+            assert np.array_equal(I0, results[leg][0]), (rank, "split_build=0: I")
+            assert np.array_equal(D0.view(np.uint64), results[leg][1].view(np.uint64)), (rank, "split_build=0: D")
             for k in ("variant", "rare_t"):
                 ctx.set_option(k, None)
         elif leg == "reps":
@@ -153,7 +164,16 @@ def run_case(name, c, ctx, rank, world):
             gs = local.allgather()
             ctx.set_option("reps_block", 100)                   # four blocks of rows
             is_rep, rep_of, rep_d = gs.greedy_reps(REPS_T, assign=True, method=gdist.METHOD_BITSET)
+            # option reps_split = 0 (reps.hip, `split`): every rank walks all
+            # the columns and joins no all-gather; the same answer bit for bit
+            # (the parent checks the default run against the oracle below)
+            ctx.set_option("reps_split", 0)
+            is_rep0, rep_of0, rep_d0 = gs.greedy_reps(REPS_T, assign=True, method=gdist.METHOD_BITSET)
+            ctx.set_option("reps_split", None)
             ctx.set_option("reps_block", None)
+            assert np.array_equal(is_rep0, is_rep), (rank, "reps_split=0: is_rep")
+            assert np.array_equal(rep_of0, rep_of), (rank, "reps_split=0: rep_of")
+            assert np.array_equal(rep_d0.view(np.uint64), rep_d.view(np.uint64)), (rank, "reps_split=0: rep_d")
             info["reps"] = (is_rep.tolist(), rep_of.tolist(), rep_d.tolist())
             continue
         elif leg == "sketch":
