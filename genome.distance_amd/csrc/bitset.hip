@@ -2694,7 +2694,13 @@ void bitset_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
     const unsigned long long* tbits = s->sparse ? s->dbits.as<unsigned long long>() : s->bits.as<unsigned long long>();
     const int64_t tW = s->sparse ? s->Wd : s->W;
     MatrixPlan& p = matrix_plan(ctx, s, r0, r1, c0, c1, upper);
-    if (p.at[4] == 0) return;   // no pair in the region
+    if (p.at[4] == 0) {         // no pair in the region: an empty kernel span (the caller reads it)
+        if (!ctx->capturing) {
+            GD_HIP(hipEventRecord(ctx->ev_k0, st));
+            GD_HIP(hipEventRecord(ctx->ev_k1, st));
+        }
+        return;
+    }
 
     // Rare kernel per call from the cost model (rare_choice): list-major opens
     // every list and walks the pairs from this block's rows with global

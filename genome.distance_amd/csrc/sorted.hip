@@ -252,7 +252,15 @@ static void launch_join(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t
         prefix[cb + 1] = prefix[cb] + std::max<int64_t>(0, rows_end - r0);
     }
     const int64_t nunits = prefix[ncb];
-    if (nunits == 0) return;
+    if (nunits == 0) {
+        // an upper-triangle region with no pair above the diagonal: nothing
+        // to count. The call still reads its kernel span (finish_timing), so
+        // the span's events are recorded, empty
+        GD_HIP(hipEventRecord(ctx->ev_k0, st));
+        GD_HIP(hipEventRecord(ctx->ev_k1, st));
+        ctx->last.launches = 0;
+        return;
+    }
     DevBuf dp((ncb + 1) * 8, st);
     h2d(dp.p, prefix.data(), (ncb + 1) * 8, st);
     GD_HIP(hipEventRecord(ctx->ev_k0, st));

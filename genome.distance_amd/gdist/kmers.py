@@ -435,6 +435,14 @@ class _Handle:
                                               C.byref(h)))
         return type(self)(self.ctx, h)
 
+    def concat(self, other):
+        """gdist_sets_concat: a new collection of this one's sets, then
+        `other`'s (kmer sets of one kmer spec, or sketches of one width): a
+        deep copy on the device, independent of both inputs."""
+        h = C.c_void_p()
+        L.check(L.lib.gdist_sets_concat(self.h, other.h, C.byref(h)))
+        return type(self)(self.ctx, h)
+
     def exchange_plan(self, method: int = L.METHOD_AUTO) -> tuple[int, float, float]:
         """(method, bytes_bitsets, bytes_codes): the exchange every rank of the
         communicator takes for a row-sharded N x N (collective call):
@@ -667,11 +675,6 @@ class KmerSets(_Handle):
         L.check(L.lib.gdist_sets_allgather_bitsets(self.ctx.h, self.h,
                                                    L.BITSET_KEEP_SINGLETONS if keep_singletons else 0,
                                                    C.byref(h)))
-        return KmerSets(self.ctx, h)
-
-    def concat(self, other: "KmerSets") -> "KmerSets":
-        h = C.c_void_p()
-        L.check(L.lib.gdist_sets_concat(self.h, other.h, C.byref(h)))
         return KmerSets(self.ctx, h)
 
     def matrix(self, rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,

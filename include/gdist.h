@@ -196,7 +196,14 @@ int  gdist_sets_pack_device(gdist_ctx* ctx, int kind, int k, unsigned flags,
  * a cache that packs each genome once (MethodTableProcessor.java:261-275 via
  * jni/GpuKmerMethod.java). Every derived representation (bitsets, tiers,
  * plans, the sorted join's index) is dropped and rebuilt on the next call;
- * the codes grow in place, doubling when full. */
+ * the codes grow in place, doubling when full.
+ * A failed append (an unencodable sequence, bad offsets: EINVAL) returns
+ * before anything of the collection is touched: its codes, every derived
+ * representation and nsets are as before the call. An append of zero
+ * sequences changes nothing and keeps built bitsets (*first = nsets). A
+ * collection from gdist_sets_upload carries no pack flags and appends with
+ * the default ones (flags 0); a gdist_sets_concat result appends with its
+ * first input's. */
 int  gdist_sets_append(gdist_ctx* ctx, gdist_sets* sets, const char* seqs, const int64_t* seq_off,
                        int64_t nseqs, int64_t* first);
 /* Adopt caller-packed sets: CSR of sorted, unique codes (host arrays, copied). */
@@ -291,7 +298,14 @@ int  gdist_sets_sparse_pairs(const gdist_sets* sets, double* pairs);
 int  gdist_sets_group_info(const gdist_sets* sets, int64_t* groups, int64_t* grouped_words);
 /* Copy the bitsets (nsets x words_per_set uint64, row-major) to the host. */
 int  gdist_sets_bitset_download(const gdist_sets* sets, uint64_t* bits);
-/* Concatenate two collections (e.g. base genomes + comparison genomes). */
+/* Concatenate two collections (e.g. base genomes + comparison genomes): a's
+ * sets, then b's, both kmer sets of one kind, k, strand and ambiguity flags
+ * (GDIST_NO_CASE_FOLD may differ) or both sketches of one width and kmer
+ * spec; anything else is EINVAL and leaves both inputs as they were. The
+ * result is a deep copy, independent of its inputs: either may be appended
+ * to or freed afterwards, and appending to the result touches neither. It
+ * holds codes (signatures) only, no derived representation, and carries a's
+ * pack flags, which a later gdist_sets_append to it uses. */
 int  gdist_sets_concat(const gdist_sets* a, const gdist_sets* b, gdist_sets** out);
 
 /* ---- distances ------------------------------------------------------- */

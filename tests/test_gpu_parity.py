@@ -222,6 +222,33 @@ def test_matrix_vs_oracle_rectangles(ctx, method):
         assert bits_equal(D, eD)
 
 
+@pytest.mark.parametrize("method", ["sorted", "bitset", "auto"])
+def test_upper_region_without_pairs(method):
+    """An upper-triangle region wholly on or left of the diagonal holds no
+    pair: the call succeeds, leaves the outputs untouched, and the calls
+    after it work. On a context of its own, as its first matrix call (the
+    sorted join used to return without recording the kernel span that the
+    call then read: EDEVICE on a context whose span was never recorded;
+    found by test_gpu_lifecycle.py::test_random_walk[1])."""
+    import gdist
+    own = gdist.Context(0)
+    try:
+        seqs = synth_sets(30, 2000, 0.05, 92)
+        sets = gdist.KmerSets.from_sequences(seqs, 15, gdist.KmerType.DNA, 0, own)
+        m = {"sorted": gdist.METHOD_SORTED, "bitset": gdist.METHOD_BITSET, "auto": gdist.METHOD_AUTO}[method]
+        for (r0, r1, c0, c1) in [(22, 24, 0, 4), (10, 20, 5, 11), (29, 30, 0, 30)]:
+            I, D = sets.matrix((r0, r1), (c0, c1), upper=True, method=m)
+            assert (I == -1).all() and np.isnan(D).all(), (r0, r1, c0, c1)
+        off, codes = oracle_pack(seqs, 15, 0, 0)
+        eI, eD = oracle.matrix(off, codes, 0, 30, 0, 30)
+        I, D = sets.matrix(method=m)
+        assert np.array_equal(I, eI) and bits_equal(D, eD)
+        again = gdist.KmerSets.from_sequences(seqs[:3], 15, gdist.KmerType.DNA, 0, own)
+        assert np.array_equal(again.matrix(method=m)[0], eI[:3, :3])
+    finally:
+        own.close()
+
+
 def test_bitset_prune_equals_keep_and_dictionary(ctx):
     import gdist
     seqs = synth_sets(150, 5000, 0.01, 92)
