@@ -1503,6 +1503,53 @@ int gdist_ctx_group_stats_timing(gdist_ctx* ctx, double* matrix_ms, double* redu
     });
 }
 
+// ---------------------------------------------------------------------------
+int gdist_within(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
+                 unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr_out, int64_t* col_out,
+                 double* d_out, int64_t* total) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_sets(sets);
+        GD_REQUIRE(sets->ctx == ctx, "sets belong to another context");
+        GD_REQUIRE(0 <= r0 && r0 <= r1 && r1 <= sets->nsets && 0 <= c0 && c0 <= c1 && c1 <= sets->nsets,
+                   "row/column range outside the set collection");
+        GD_REQUIRE(max_dist == max_dist, "max_dist is NaN");
+        GD_REQUIRE(capacity >= 0, "negative capacity");
+        GD_REQUIRE(rowptr_out && total, "null rowptr_out or total");
+        GD_REQUIRE(capacity == 0 || (col_out && d_out), "null col_out or d_out with capacity > 0");
+        GD_REQUIRE(!(flags & GDIST_OUT_DEVICE), "gdist_within does not support GDIST_OUT_DEVICE");
+        const bool sketch = sets->kind == GDIST_SKETCH;
+        if (sketch) {
+            check_codes(sets);
+        } else {
+            GD_REQUIRE(method >= GDIST_METHOD_AUTO && method <= GDIST_METHOD_BITSET, "unknown method");
+            GD_REQUIRE(method != GDIST_METHOD_SORTED || sets->has_codes, "this collection holds bitsets only");
+        }
+        GD_REQUIRE(sets->nsets < (int64_t)UINT32_MAX, "too many sets for 32-bit column keys");
+        const int64_t nr = r1 - r0, nc = c1 - c0;
+        auto* s = const_cast<gdist_sets*>(sets);
+        int m = GDIST_METHOD_AUTO;
+        if (!sketch && nr > 0 && nc > 0) m = resolve_method(ctx, s, method, (double)nr * (double)nc);
+        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
+        ctx->last = Timing{};
+        // the row pointers into a local first: a failure on the device leaves them and *total untouched
+        std::vector<int64_t> rp((size_t)nr + 1, 0);
+        gdist::within(ctx, s, r0, r1, c0, c1, m, flags, max_dist, capacity, rp.data(), col_out, d_out);
+        std::copy(rp.begin(), rp.end(), rowptr_out);
+        *total = rp[(size_t)nr];
+    });
+}
+
+int gdist_ctx_within_timing(gdist_ctx* ctx, double* matrix_ms, double* select_ms) {
+    return guard([&] {
+        GD_REQUIRE(ctx != nullptr, "null context");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        if (matrix_ms) *matrix_ms = ctx->within_matrix_ms;
+        if (select_ms) *select_ms = ctx->within_select_ms;
+    });
+}
+
 int gdist_comm_unique_id(char id[GDIST_UNIQUE_ID_BYTES]) {
     return guard([&] {
         static_assert(sizeof(ncclUniqueId) <= GDIST_UNIQUE_ID_BYTES, "unique id size");

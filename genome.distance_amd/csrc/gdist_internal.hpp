@@ -345,6 +345,8 @@ struct gdist_ctx {
     double closest_matrix_ms = -1.0, closest_select_ms = -1.0;
     // the same for the last gdist_group_stats call: matrix kernels, reduce kernel
     double group_matrix_ms = -1.0, group_reduce_ms = -1.0;
+    // the same for the last gdist_within call: matrix kernels, count + scan + write kernels
+    double within_matrix_ms = -1.0, within_select_ms = -1.0;
     gdist_ctx() { for (auto& o : opt) o = gdist::kOptUnset; }
     int64_t option(gdist::Opt o, int64_t dflt) const { return opt[o] == gdist::kOptUnset ? dflt : opt[o]; }
     bool has_option(gdist::Opt o) const { return opt[o] != gdist::kOptUnset; }
@@ -717,6 +719,14 @@ void closest(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, 
 // labels: host, [ntypes][nsets]; out: [ntypes][2], bad: [ntypes], written whole
 void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
                  unsigned flags, int ntypes, const int32_t* labels, gdist_group_side* out, int64_t* bad);
+
+// within.hip — every pair within max_dist as CSR (gdist_within)
+// method: SORTED or BITSET (resolved by the caller); ignored for sketches.
+// rowptr: r1 - r0 + 1 entries, written whole; col_out / d_out: the first
+// min(total, capacity) entries of the row-major order
+int64_t within_rows(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem);
+void within(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
+            unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr, int64_t* col_out, double* d_out);
 
 // lsh.hip
 void lsh_build(gdist_ctx* ctx, const gdist_sets* sk, int stages, int buckets, uint64_t seed, gdist_lsh* L);

@@ -133,6 +133,14 @@ class Context:
         L.check(L.lib.gdist_ctx_group_stats_timing(self.h, C.byref(m), C.byref(s)))
         return m.value, s.value
 
+    def within_timing(self) -> tuple[float, float]:
+        """(matrix kernels ms, count + scan + write kernels ms) of the last
+        within() call made with option time_kernels = 1, summed over its steps
+        (-1: not timed)."""
+        m, s = C.c_double(), C.c_double()
+        L.check(L.lib.gdist_ctx_within_timing(self.h, C.byref(m), C.byref(s)))
+        return m.value, s.value
+
     def recent_timings(self, n: int) -> list[float]:
         """Kernel ms of the last n matrix calls, oldest first (waits for them)."""
         out = np.zeros(max(n, 1), dtype=np.float64)
@@ -415,6 +423,34 @@ class _Handle:
         L.check(L.lib.gdist_group_stats(self.ctx.h, self.h, r0, r1, c0, c1, method, fl, T, L.ptr(buf, C.c_int32),
                                         C.addressof(sides), bad))
         return GroupStats(sides, bad)
+
+    # first capacity guess of within(capacity=None): entries a row of the call
+    WITHIN_GUESS_PER_ROW = 64
+
+    def _within(self, max_dist: float, rows, cols, upper: bool, method: int, flags: int, keep_self: bool,
+                capacity: int | None):
+        """gdist_within over rows x cols: (rowptr int64[nr + 1], cols int64[m], d float64[m]),
+        m = min(total, capacity); capacity None: the complete list (a guess,
+        then a second call when the total exceeds it)."""
+        ns = len(self)
+        r0, r1 = rows or (0, ns)
+        c0, c1 = cols or (0, ns)
+        nr = max(r1 - r0, 0)
+        fl = flags | (L.UPPER_TRIANGLE if upper else 0) | (L.CLOSEST_KEEP_SELF if keep_self else 0)
+        rowptr = np.zeros(nr + 1, dtype=np.int64)
+        total = C.c_int64(0)
+        cap = int(capacity) if capacity is not None else max(nr, 1) * self.WITHIN_GUESS_PER_ROW
+        while True:
+            # non-empty buffers behind empty results: the library is never handed a null output
+            col = np.zeros(max(cap, 1), dtype=np.int64)
+            d = np.zeros(max(cap, 1), dtype=np.float64)
+            L.check(L.lib.gdist_within(self.ctx.h, self.h, r0, r1, c0, c1, method, fl, float(max_dist), cap,
+                                       L.ptr(rowptr, C.c_int64), L.ptr(col, C.c_int64), L.ptr(d, C.c_double),
+                                       C.byref(total)))
+            if capacity is not None or total.value <= cap:
+                m = min(total.value, cap)
+                return rowptr, col[:m], d[:m]
+            cap = total.value
 
     def getClosest(self, n: int, max_dist: float, **kw) -> list[list[tuple[int, float]]]:
         """getClosest(kmers, n, maxDist) for every row of closest(n, max_dist, **kw)
@@ -709,6 +745,18 @@ class KmerSets(_Handle):
         -1 / 1.0. d is bit-identical to matrix()'s D; the N x N stays on the device."""
         return self._closest(n, max_dist, rows, cols, method, flags, keep_self)
 
+    def within(self, max_dist: float, rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,
+               upper: bool = False, method: int = L.METHOD_AUTO, flags: int = 0, keep_self: bool = False,
+               capacity: int | None = None):
+        """Every pair within a distance (gdist_within): the pairs (i, j) of rows x
+        cols with Jaccard distance <= max_dist, row ascending then column
+        ascending, as CSR: (rowptr int64[nr + 1], cols int64[m], d float64[m]).
+        The set itself is left out unless keep_self; upper: only j > i.
+        capacity None: the complete list; a number: at most that many entries
+        (m = min(total, capacity)), rowptr still the full counts. d is
+        bit-identical to matrix()'s D; the N x N stays on the device."""
+        return self._within(max_dist, rows, cols, upper, method, flags, keep_self, capacity)
+
     def group_stats(self, labels, rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,
                     upper: bool = True, method: int = L.METHOD_AUTO, flags: int = 0) -> GroupStats:
         """In-group / out-group summary of the distances of rows x cols
@@ -822,6 +870,14 @@ class SketchSets(_Handle):
         SKETCH_JACCARD, EMPTY_NAN): the same result shape as KmerSets.closest, d
         bit-identical to matrix()'s D."""
         return self._closest(n, max_dist, rows, cols, L.METHOD_AUTO, flags, keep_self)
+
+    def within(self, max_dist: float, rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,
+               upper: bool = False, method: int = L.METHOD_AUTO, flags: int = 0, keep_self: bool = False,
+               capacity: int | None = None):
+        """Every pair within a sketch distance (gdist_within; flags:
+        SKETCH_JACCARD, EMPTY_NAN; method is ignored): as KmerSets.within, d
+        bit-identical to matrix()'s D."""
+        return self._within(max_dist, rows, cols, upper, L.METHOD_AUTO, flags, keep_self, capacity)
 
     def group_stats(self, labels, rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,
                     upper: bool = True, method: int = L.METHOD_AUTO, flags: int = 0) -> GroupStats:

@@ -5,6 +5,7 @@ errors and output format, and replaces its per-pair Java loop with whole
 row-block / row-query calls on the device:
 
   fasta_distance   FastaDistanceProcessor  (fastaDist)  FastaDistanceProcessor.java:84-194
+  fasta_close_pairs  the fastaDist lines with distance <= max_dist (KmerSets.within)
   genome_distance  GenomeProcessor         (genomes)    GenomeProcessor.java:74-150
   fasta_reps       FastaDistanceRepsProcessor (fastaReps) FastaDistanceRepsProcessor.java:58-149
   distance_reps    DistanceRepsProcessor   (distReps)   DistanceRepsProcessor.java:140-275
@@ -82,10 +83,40 @@ def fasta_distance(records: Sequence[FastaRecord], out: TextIO, kmer_size: int =
     return pairs
 
 
+def fasta_close_pairs(records: Sequence[FastaRecord], out: TextIO, max_dist: float, kmer_size: int = 0,
+                      kmer_type: KmerType = KmerType.DNA, flags: int = 0, method: int = L.METHOD_AUTO,
+                      ctx: Context | None = None) -> int:
+    """fastaDist restricted to the close pairs: the header, then exactly those
+    lines of fasta_distance whose distance is <= max_dist, in the same order,
+    from one KmerSets.within(upper=True) call; the N×N stays on the device.
+    Returns the lines written."""
+    k = kmer_size or kmer_type.getKmerSize()
+    if k < 2:
+        raise ParseFailureException("Kmer size must be at least 2.")
+    out.write("seq1\tname1\tseq2\tname2\tdistance\n")
+    n = len(records)
+    if n < 2:
+        return 0
+    sets = KmerSets.from_sequences([r.sequence for r in records], k, kmer_type, flags, ctx)
+    if method == L.METHOD_BITSET:
+        sets.build_bitsets()
+    rowptr, cols, d = sets.within(max_dist, upper=True, method=method)
+    for a in range(n):
+        ra = records[a]
+        for p in range(rowptr[a], rowptr[a + 1]):
+            rb = records[cols[p]]
+            out.write(f"{ra.label}\t{ra.comment}\t{rb.label}\t{rb.comment}\t{java_double(d[p])}\n")
+    return int(rowptr[n])
+
+
 def genome_distance(base: Sequence[Genome], others: Sequence[Sequence[Genome]], out: TextIO,
                     kmer_size: int = 21, max_dist: float = 0.9, flags: int = 0,
-                    method: int = L.METHOD_AUTO, ctx: Context | None = None) -> int:
-    """genomes: every comparison genome against every base genome."""
+                    method: int = L.METHOD_AUTO, ctx: Context | None = None, within: bool = False) -> int:
+    """genomes: every comparison genome against every base genome. The
+    reference validates max_dist and then writes every pair
+    (GenomeProcessor.java:140-144); within=True applies the filter its usage
+    text documents (GenomeProcessor.java:35): only the pairs with distance <=
+    max_dist are written, from one KmerSets.within call."""
     if kmer_size < 4:
         raise ParseFailureException("Kmer size cannot be less than 4.")          # GenomeProcessor.java:84-85
     if max_dist <= 0.0 or max_dist > 1.0:
@@ -97,6 +128,12 @@ def genome_distance(base: Sequence[Genome], others: Sequence[Sequence[Genome]], 
     allg = list(base) + comps
     sets = KmerSets.from_sequences([g.kmer_text() for g in allg], kmer_size, KmerType.DNA, flags, ctx)
     nb = len(base)
+    if within:
+        rowptr, cols, d = sets.within(max_dist, rows=(nb, len(allg)), cols=(0, nb), method=method)
+        for a, g in enumerate(comps):
+            for p in range(rowptr[a], rowptr[a + 1]):
+                out.write(f"{g.id}\t{base[cols[p]].id}\t{java_double(d[p])}\n")
+        return int(rowptr[len(comps)])
     # one rectangle: rows = comparison genomes, cols = base genomes (GenomeProcessor.java:140)
     _, D = sets.matrix((nb, len(allg)), (0, nb), method=method, want_I=False)
     n = 0

@@ -27,6 +27,8 @@
  *   gdist_closest          getClosest(kmers, n, maxDist), exhaustively
  *                          (every column, no LSH buckets)        MashProcessor.java:150, FindProcessor.java:110
  *                          --maxDist of the genomes table        GenomeProcessor.java:58-60,89
+ *   gdist_within           the documented -m filter of the table GenomeProcessor.java:35
+ *                          (every pair with d <= maxDist)
  *   gdist_group_stats      recordDistance over a distance table  GroupTypeSpec.java:77-95
  *                          in / out-group min, mean, sd, max     DistanceCheckProcessor.java:200-223
  *   gdist_sets_allgather   (new) RCCL all-gather of packed sets for row-sharded N×N
@@ -462,6 +464,52 @@ int  gdist_group_stats_merge(gdist_group_side* acc, int64_t* bad_acc, const gdis
  * call made with option "time_kernels" = 1: the matrix kernels and the reduce
  * kernel apart; -1 when the call was not timed. */
 int  gdist_ctx_group_stats_timing(gdist_ctx* ctx, double* matrix_ms, double* reduce_ms);
+
+/* ---- every pair within a distance -------------------------------------- */
+/* The documented maxDist filter of the genomes table (GenomeProcessor.java:35,
+ * "if a comparison results in a distance greater than this value, it will not
+ * be output") as a CSR list, without the distance table leaving the device:
+ * every pair (i, j), i in [r0, r1), j in [c0, c1), with d(i, j) <= max_dist.
+ * The comparison is a plain fp64 <=: NaN (GDIST_EMPTY_NAN) never qualifies,
+ * d == 1.0 does when max_dist >= 1.0, a negative max_dist gives nothing and
+ * +inf everything but NaN. j == i is left out unless GDIST_CLOSEST_KEEP_SELF;
+ * with GDIST_UPPER_TRIANGLE only j > i counts (supported here, unlike
+ * gdist_closest: the fastaDist table is the upper triangle). d is the bit
+ * pattern gdist_intersect_matrix (kmer sets: method AUTO / SORTED / BITSET
+ * resolved as gdist_closest resolves it) or gdist_sketch_matrix (GDIST_SKETCH
+ * collections: method ignored, GDIST_SKETCH_JACCARD honoured) writes with the
+ * same flags.
+ *
+ * Order: row ascending, column ascending within a row; it depends on nothing
+ * else (not the method, not "closest_rows", not the run). rowptr_out[a] is
+ * the number of qualifying pairs in rows r0 .. r0 + a - 1, always complete
+ * whatever capacity is, and *total = rowptr_out[r1 - r0]. col_out (global set
+ * indices) and d_out receive the first min(*total, capacity) entries of that
+ * order: a row may be cut in the middle, and nothing at or past capacity is
+ * touched. capacity == 0 is the counting call: col_out and d_out may be NULL
+ * and no survivor is written on the device either. A caller counts and calls
+ * again, or guesses a capacity and calls again when *total > capacity.
+ *
+ * An empty row or column range: GDIST_OK, rowptr all zero, total 0. Disjoint
+ * row ranges concatenate (shift the later rowptr by the earlier total), so
+ * the ranks of a row-sharded run need no merge call. The walk is by row
+ * blocks only (option "closest_rows", default by memory; "closest_cols" is
+ * not read): per block the matrix kernels leave I or D on the device, a count
+ * kernel, a scan and a write kernel compact it, and for kmer sets D is never
+ * written. EINVAL, decided before any work (every output stays untouched): a
+ * bad range, NaN max_dist, capacity < 0, null rowptr_out or total, null
+ * col_out or d_out with capacity > 0, GDIST_OUT_DEVICE, an unknown method,
+ * SORTED on a bitsets-only collection, 2^32 - 1 sets or more. After any other
+ * failure the contents of col_out and d_out are unspecified. */
+int  gdist_within(gdist_ctx* ctx, const gdist_sets* sets,
+                  int64_t r0, int64_t r1, int64_t c0, int64_t c1,
+                  int method, unsigned flags, double max_dist, int64_t capacity,
+                  int64_t* rowptr_out /* r1 - r0 + 1 */, int64_t* col_out, double* d_out,
+                  int64_t* total);
+/* HIP-event time (ms, summed over the steps) of the last gdist_within call
+ * made with option "time_kernels" = 1: the matrix kernels and the count, scan
+ * and write kernels apart; -1 when the call was not timed. */
+int  gdist_ctx_within_timing(gdist_ctx* ctx, double* matrix_ms, double* select_ms);
 
 /* ---- multi-GPU (RCCL over xGMI) -------------------------------------- */
 #define GDIST_UNIQUE_ID_BYTES 128

@@ -43,6 +43,8 @@ public final class GpuKmerSets implements AutoCloseable {
                                      double[] out, int ld);
     static native void nClosest(long ctx, long sets, long r0, long r1, long c0, long c1, int method, int flags,
                                 int n, double maxDist, long[] idx, double[] d, int[] count);
+    static native long nWithin(long ctx, long sets, long r0, long r1, long c0, long c1, int method, int flags,
+                               double maxDist, long[] rowptr, long[] cols, double[] d);
 
     /** One device context (gdist_ctx): serialises its calls, shared by threads. */
     public static final class Context implements AutoCloseable {
@@ -118,6 +120,20 @@ public final class GpuKmerSets implements AutoCloseable {
                         long[] idx, double[] d, int[] count) {
         nClosest(ctx, handle, r0, r1, c0, c1, METHOD_AUTO, keepSelf ? CLOSEST_KEEP_SELF : 0, n, maxDist, idx, d,
                  count);
+    }
+
+    /** Every pair (i, j), i in [r0, r1), j in [c0, c1), with distance <= maxDist
+     *  (gdist_within; the documented filter of GenomeProcessor.java:35), row ascending
+     *  then column ascending, as CSR: rowptr[a] = the pairs of rows r0 .. r0 + a - 1
+     *  (r1 - r0 + 1 entries, always complete), cols / d = the first min(total,
+     *  min(cols.length, d.length)) pairs. Returns the total: when it exceeds the
+     *  arrays, call again with arrays that long. The set itself is left out unless
+     *  keepSelf; upperTriangle: only j > i. Works on kmer sets and on sketch collections. */
+    public long within(long r0, long r1, long c0, long c1, double maxDist, boolean upperTriangle, boolean keepSelf,
+                       long[] rowptr, long[] cols, double[] d) {
+        return nWithin(ctx, handle, r0, r1, c0, c1, METHOD_AUTO,
+                       (upperTriangle ? UPPER_TRIANGLE : 0) | (keepSelf ? CLOSEST_KEEP_SELF : 0), maxDist, rowptr,
+                       cols, d);
     }
 
     /** Both passes of DistanceRepsProcessor.java:185-262 in one call: isRep[i] = 1

@@ -416,3 +416,34 @@ JNIEXPORT void JNICALL JFN(nClosest)(JNIEnv* env, jclass c, jlong ctx, jlong set
     free(vi); free(vd); free(vc);
     if (rc) throw_for(env, rc);
 }
+
+/* ---- every pair within maxDist as CSR (gdist_within): rowptr holds r1 - r0 + 1
+ * entries and is always complete; cols / d receive the first min(total,
+ * capacity) pairs, capacity = min(cols.length, d.length); returns the total */
+JNIEXPORT jlong JNICALL JFN(nWithin)(JNIEnv* env, jclass c, jlong ctx, jlong sets, jlong r0, jlong r1, jlong c0,
+                                     jlong c1, jint method, jint flags, jdouble maxDist, jlongArray rowptr,
+                                     jlongArray cols, jdoubleArray d) {
+    const int64_t nr = (int64_t)r1 - (int64_t)r0;
+    if (nr < 0) { throw_arg(env, "negative row range"); return 0; }
+    if (too_short(env, rowptr, nr + 1, "rowptr shorter than r1 - r0 + 1") ||
+        too_short(env, cols, 0, "null cols") || too_short(env, d, 0, "null d"))
+        return 0;
+    const int64_t nc = (*env)->GetArrayLength(env, cols), nd = (*env)->GetArrayLength(env, d);
+    const int64_t cap = nc < nd ? nc : nd;
+    int64_t* vr = malloc(((size_t)nr + 1) * sizeof(int64_t));
+    int64_t* vc = malloc(((size_t)cap + 1) * sizeof(int64_t));
+    double* vd = malloc(((size_t)cap + 1) * sizeof(double));
+    if (!vr || !vc || !vd) { free(vr); free(vc); free(vd); throw_oom(env); return 0; }
+    int64_t total = 0;
+    int rc = gdist_within(CTX(ctx), SETS(sets), r0, r1, c0, c1, method, (unsigned)flags, maxDist, cap, vr, vc, vd,
+                          &total);
+    if (!rc) {
+        const int64_t m = total < cap ? total : cap;
+        (*env)->SetLongArrayRegion(env, rowptr, 0, (jsize)(nr + 1), (const jlong*)vr);
+        (*env)->SetLongArrayRegion(env, cols, 0, (jsize)m, (const jlong*)vc);
+        (*env)->SetDoubleArrayRegion(env, d, 0, (jsize)m, vd);
+    }
+    free(vr); free(vc); free(vd);
+    if (rc) { throw_for(env, rc); return 0; }
+    return (jlong)total;
+}
