@@ -537,8 +537,9 @@ __device__ __forceinline__ void rare_slab_row(const RareSlab& rs, int unit, int6
 
 // ---- the sparse tile kernel ---------------------------------------------
 // One workgroup per (128 x 128 tile of absolute set blocks (A, B), chunk of
-// the sparse words). Each wave takes 64 sparse words at a time: lane l loads
-// the (A, s) and (B, s) entry ranges of word s = base + l, the wave
+// the sparse words). Each wave takes a batch of at most kBatchWords sparse
+// words at a time: lane l loads the starts of the (A, s) and (B, s) entry
+// lists of word s = base + l (their ends are the next lane's starts), the wave
 // prefix-sums the word's product slots, parks the walk fields in LDS, and the
 // 64 lanes then walk the flattened slots, SUN per lane in flight so their
 // loads overlap, adding popc(c_i & c_j) to LDS counters. A diagonal tile
@@ -596,6 +597,28 @@ struct SparseWalk {
 __device__ __forceinline__ int slot_rec(int last, int gb, unsigned long long m) {
     const int before = __popcll(__ballot(last < gb));
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, (uint32_t)before));
+}
+
+// The inclusive sum of v over the wave's 64 lanes by DPP adds, no LDS round
+// trip (a __shfl_up scan is six ds_bpermute_b32): within each row of 16 lanes
+// row_shr 1, 2, 4, 8 (a lane without a source adds 0), then lane 15 of rows 0
+// and 2 into rows 1 and 3 (row_bcast:15), then lane 31 into rows 2 and 3
+// (row_bcast:31). Every lane must be active. These DPP controls exist on the
+// gfx9 family only, which is all this library builds for.
+__device__ __forceinline__ int wave_scan_incl(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);    // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);    // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);    // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);    // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);   // row_bcast:15 row_mask:0xa
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);   // row_bcast:31 row_mask:0xc
+    return v;
+}
+
+// lane l + 1's v (lane 63: 0), one DPP move (wave_shl:1; gfx9 family, every
+// lane active, as above)
+__device__ __forceinline__ uint32_t wave_next_lane(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xF, 0xF, true);
 }
 
 // Diagonal tiles: slot q of a word is its pair (y, x), y < x, q = x(x-1)/2 +
@@ -847,10 +870,10 @@ __device__ __forceinline__ void sparse_walk(const int4* __restrict__ rec, unsign
 // The tile being walked (sparse_tile_kernel): its blocks' (block, word)
 // offsets, bases of the chunk's records, row trimming, shape flags.
 struct TileWalk {
-    const int64_t* offA;
-    const int64_t* offB;
+    const uint32_t* offA;                 // the int64 offsets as dwords: entries < 2^28 in all, so an
+    const uint32_t* offB;                 // offset is its low dword, [2 s] of this view
     const ulonglong2* ent;
-    int64_t ra0, cb0;                     // chunk bases (entries < 2^28 in all: byte offsets)
+    uint32_t ra0, cb0;                    // chunk bases (entries < 2^28 in all: byte offsets)
     uint32_t zA, zB;                      // the sentinel run from those bases
     SparseWalk e;
     int rlo, rhi;
@@ -866,26 +889,34 @@ template <int SUN, int MT>
 __device__ __forceinline__ void global_batch(const TileWalk& tc, int64_t s0, int64_t be, int only, int lane,
                                              int4* __restrict__ wrec, unsigned long long* __restrict__ masks,
                                              uint32_t* __restrict__ cnt) {
-    const int64_t* offA = tc.offA;
-    const int64_t* offB = tc.offB;
+    const uint32_t* offA = tc.offA;
+    const uint32_t* offB = tc.offB;
     const ulonglong2* ent = tc.ent;
-    const int64_t ra0 = tc.ra0, cb0 = tc.cb0;
+    const uint32_t ra0 = tc.ra0, cb0 = tc.cb0;
     const uint32_t zA = tc.zA, zB = tc.zB;
     const SparseWalk& e = tc.e;
     const int rlo = tc.rlo, rhi = tc.rhi;
     const bool rpart = tc.rpart, diag = tc.diag, mirror = tc.mirror, r22 = tc.r22;
     const bool d22 = MT == 2 && tc.d22;
     const bool wtail = tc.wtail;
-    const int64_t s = s0 + lane;
-    int64_t rb = ra0, cb = cb0;
+    // each bound is loaded once: lane l <= bn takes the starts of word s0 + l
+    // (lane bn: the ends of the batch's last word), and a word's lists end
+    // where the next lane's start
+    const int bn = be - s0 < kBatchWords ? (int)(be - s0) : kBatchWords;
+    uint32_t rb = ra0, cb = cb0;
+    if (lane <= bn) {
+        rb = offA[2 * (s0 + lane)];
+        cb = offB[2 * (s0 + lane)];
+    }
+    const uint32_t re = wave_next_lane(rb), ce = wave_next_lane(cb);
     int nr = 0, ncl = 0;
-    if (lane < kBatchWords && s < be && (only < 0 || lane == only)) {
-        rb = offA[s]; nr = (int)(offA[s + 1] - rb);
-        cb = offB[s]; ncl = (int)(offB[s + 1] - cb);
+    if (lane < bn && (only < 0 || lane == only)) {
+        nr = (int)(re - rb);
+        ncl = (int)(ce - cb);
         if (rpart) {                               // lists are sorted by set: trim both ends
             int a = 0, en = nr;
             for (int t = 0; t < nr; t++) {
-                const int st = (int)((uint32_t)ent[rb + t].x >> 8);   // row code: set << 8 | rotation key
+                const int st = (int)((uint32_t)ent[(int64_t)rb + t].x >> 8);   // row code: set << 8 | rotation key
                 a += st < rlo;
                 en -= st >= rhi;
             }
@@ -897,12 +928,7 @@ __device__ __forceinline__ void global_batch(const TileWalk& tc, int64_t s0, int
     const int hp = (nr + 1) >> 1;                 // 2 x 2 diagonal: pairs of entries
     const int P = diag ? (d22 ? (nr >= 2 ? hp * (hp + 1) / 2 : 0) : nr * (nr - 1) / 2)
                        : (r22 ? hp : nr) * ncd;
-    int incl = P;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
+    const int incl = wave_scan_incl(P);
     const int total = __builtin_amdgcn_readlane(incl, 63);      // uniform: the walk's loop stays scalar
     // the records of the words with slots, compacted in slot order, and the
     // virtual word after them (its records: the zero sentinel run)
@@ -1008,7 +1034,8 @@ __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
     const int64_t ra0 = offA[sb], cb0 = offB[sb];           // chunk bases (entries < 2^28 in all: byte offsets)
     const int64_t ntot = off[(int64_t)ceil_div(N, SB) * Ws];         // entries of every block: the sentinel run
     const uint32_t zA = (uint32_t)(ntot - ra0), zB = (uint32_t)(ntot - cb0);
-    const TileWalk tc{offA, offB, ent, ra0, cb0, zA, zB,
+    const TileWalk tc{reinterpret_cast<const uint32_t*>(offA), reinterpret_cast<const uint32_t*>(offB), ent,
+                      (uint32_t)ra0, (uint32_t)cb0, zA, zB,
                       SparseWalk{reinterpret_cast<const char*>(ent + ra0), reinterpret_cast<const char*>(ent + cb0)},
                       rlo, rhi, rpart, diag, mirror, r22, diag22 != 0, wtail != 0};
     int4* wrec = &rec[wv][0];
@@ -1038,7 +1065,7 @@ __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
         if (dyn) {
             int nb = 0;
             if (lane == 0) nb = atomicAdd(&next_batch, 1);
-            s0 = sb + (int64_t)__builtin_amdgcn_readfirstlane(__shfl(nb, 0, 64)) * bw;
+            s0 = sb + (int64_t)__builtin_amdgcn_readfirstlane(nb) * bw;    // lane 0 is active: its claim
         } else {
             s0 += bw;
         }
