@@ -1550,6 +1550,46 @@ int gdist_ctx_within_timing(gdist_ctx* ctx, double* matrix_ms, double* select_ms
     });
 }
 
+// ---------------------------------------------------------------------------
+int gdist_pairs(gdist_ctx* ctx, const gdist_sets* sets, int64_t npairs, const int64_t* rows, const int64_t* cols,
+                int method, unsigned flags, int32_t* I_out, double* D_out) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_sets(sets);
+        GD_REQUIRE(sets->ctx == ctx, "sets belong to another context");
+        GD_REQUIRE(sets->kind != GDIST_SKETCH, "pair lists run on kmer sets");
+        GD_REQUIRE(npairs >= 0 && npairs < (int64_t(1) << 31), "npairs outside 0 .. 2^31 - 1");
+        GD_REQUIRE(!(flags & (GDIST_UPPER_TRIANGLE | GDIST_OUT_DEVICE)),
+                   "gdist_pairs supports neither GDIST_UPPER_TRIANGLE nor GDIST_OUT_DEVICE");
+        GD_REQUIRE(method >= GDIST_METHOD_AUTO && method <= GDIST_METHOD_BITSET, "unknown method");
+        GD_REQUIRE(method != GDIST_METHOD_SORTED || sets->has_codes, "this collection holds bitsets only");
+        GD_REQUIRE(npairs == 0 || (rows && cols), "null rows or cols");
+        GD_REQUIRE(npairs == 0 || I_out || D_out, "both outputs null");
+        for (int64_t p = 0; p < npairs; p++)
+            GD_REQUIRE(rows[p] >= 0 && rows[p] < sets->nsets && cols[p] >= 0 && cols[p] < sets->nsets,
+                       "pair index out of range");
+        ctx->pairs_kernel_ms = -1.0;
+        ctx->pairs_groups = ctx->pairs_units = 0;
+        if (npairs == 0) return;
+        auto* s = const_cast<gdist_sets*>(sets);
+        const int m = resolve_method(ctx, s, method, (double)npairs);
+        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
+        ctx->last = Timing{};
+        gdist::pairs(ctx, s, m, flags, npairs, rows, cols, I_out, D_out);
+    });
+}
+
+int gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, int64_t* units) {
+    return guard([&] {
+        GD_REQUIRE(ctx != nullptr, "null context");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        if (kernel_ms) *kernel_ms = ctx->pairs_kernel_ms;
+        if (groups) *groups = ctx->pairs_groups;
+        if (units) *units = ctx->pairs_units;
+    });
+}
+
 int gdist_comm_unique_id(char id[GDIST_UNIQUE_ID_BYTES]) {
     return guard([&] {
         static_assert(sizeof(ncclUniqueId) <= GDIST_UNIQUE_ID_BYTES, "unique id size");

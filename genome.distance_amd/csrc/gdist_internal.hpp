@@ -347,6 +347,10 @@ struct gdist_ctx {
     double group_matrix_ms = -1.0, group_reduce_ms = -1.0;
     // the same for the last gdist_within call: matrix kernels, count + scan + write kernels
     double within_matrix_ms = -1.0, within_select_ms = -1.0;
+    // the last gdist_pairs call: its kernels' time (option time_kernels = 1, else -1),
+    // the distinct-row groups of its list and the work units launched for them
+    double pairs_kernel_ms = -1.0;
+    int64_t pairs_groups = 0, pairs_units = 0;
     gdist_ctx() { for (auto& o : opt) o = gdist::kOptUnset; }
     int64_t option(gdist::Opt o, int64_t dflt) const { return opt[o] == gdist::kOptUnset ? dflt : opt[o]; }
     bool has_option(gdist::Opt o) const { return opt[o] != gdist::kOptUnset; }
@@ -727,6 +731,12 @@ void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t 
 int64_t within_rows(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem);
 void within(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
             unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr, int64_t* col_out, double* d_out);
+
+// pairs.hip — the distances of a pair list (gdist_pairs)
+// method: SORTED or BITSET (resolved by the caller, every argument checked);
+// rows / cols / I_out / D_out: host, n entries, either output may be null
+void pairs(gdist_ctx* ctx, const gdist_sets* s, int method, unsigned flags, int64_t n, const int64_t* rows,
+           const int64_t* cols, int32_t* I_out, double* D_out);
 
 // lsh.hip
 void lsh_build(gdist_ctx* ctx, const gdist_sets* sk, int stages, int buckets, uint64_t seed, gdist_lsh* L);

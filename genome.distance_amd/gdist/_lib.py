@@ -153,6 +153,8 @@ _SIGS = {
     "gdist_within": (C.c_int, [_ctxp, _setp, _i64, _i64, _i64, _i64, C.c_int, _u32, _dbl, _i64, _i64p, _i64p, _dblp,
                                _i64p]),
     "gdist_ctx_within_timing": (C.c_int, [_ctxp, _dblp, _dblp]),
+    "gdist_pairs": (C.c_int, [_ctxp, _setp, _i64, _i64p, _i64p, C.c_int, _u32, _i32p, _dblp]),
+    "gdist_ctx_pairs_info": (C.c_int, [_ctxp, _dblp, _i64p, _i64p]),
     "gdist_comm_unique_id": (C.c_int, [C.c_char_p]),
     "gdist_comm_init": (C.c_int, [_ctxp, C.c_char_p, C.c_int, C.c_int]),
     "gdist_comm_init_host": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_void_p, _vp]),

@@ -767,6 +767,34 @@ class KmerSets(_Handle):
         exact, so the result does not depend on method or block sizes."""
         return self._group_stats(labels, rows, cols, upper, method, flags)
 
+    def pairs(self, rows, cols, method: int = L.METHOD_AUTO, flags: int = 0, want_I: bool = True,
+              want_D: bool = True):
+        """Distances of a pair list (gdist_pairs): for every p the intersection
+        count and distance of sets (rows[p], cols[p]), in one device call:
+        (I int32[P] | None, D float64[P] | None). Any order, repeats and i == j
+        allowed; both are matrix()'s I and D of that cell bit for bit."""
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        c = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
+        if len(r) != len(c):
+            raise ValueError(f"{len(r)} rows but {len(c)} cols")
+        n = len(r)
+        I = np.full(n, -1, dtype=np.int32) if want_I else None
+        D = np.full(n, np.nan, dtype=np.float64) if want_D else None
+        L.check(L.lib.gdist_pairs(self.ctx.h, self.h, n, L.ptr(r, C.c_int64) if n else None,
+                                  L.ptr(c, C.c_int64) if n else None, method, flags,
+                                  L.ptr(I, C.c_int32) if want_I and n else None,
+                                  L.ptr(D, C.c_double) if want_D and n else None))
+        return I, D
+
+    def pairs_info(self) -> tuple[float, int, int]:
+        """(kernel ms, groups, units) of the context's last pairs() call
+        (gdist_ctx_pairs_info): the kernel time is -1 unless option
+        time_kernels = 1; groups are the distinct rows of the list, units the
+        work units launched for them."""
+        ms, g, u = C.c_double(), C.c_int64(), C.c_int64()
+        L.check(L.lib.gdist_ctx_pairs_info(self.ctx.h, C.byref(ms), C.byref(g), C.byref(u)))
+        return ms.value, g.value, u.value
+
     def row_query(self, q: int, cols: Iterable[int], mode: int = L.QUERY_ALL, t: float = 1.0):
         cl = np.ascontiguousarray(np.fromiter(cols, dtype=np.int64))
         D = np.zeros(max(len(cl), 1), dtype=np.float64)

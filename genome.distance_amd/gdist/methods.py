@@ -129,6 +129,26 @@ class DistanceMethod:
         with measurer._lock:
             measurer._row.update(row)
 
+    def pair_distances(self, pairs: Sequence[tuple[Genome, Genome]]) -> list[float]:
+        """The distances of a whole pair list in ONE device call: every genome
+        of the list packed once into one collection (first appearance), then
+        gdist_pairs over the (id1, id2) positions (the list the reference walks
+        pair by pair, MethodTableProcessor.java:258-276)."""
+        if not pairs:
+            return []
+        index: dict[str, int] = {}
+        texts = []
+        for g in (g for p in pairs for g in p):
+            if g.id not in index:
+                index[g.id] = len(texts)
+                texts.append(self.kmer_text(g))
+        sets = KmerSets.from_sequences(texts, self.k, self.kmer_type, self.flags, self.ctx)
+        try:
+            _, d = sets.pairs([index[a.id] for a, _ in pairs], [index[b.id] for _, b in pairs], want_I=False)
+        finally:
+            sets.free()
+        return [float(x) for x in d]
+
     def close(self) -> None:
         pass
 
@@ -276,12 +296,16 @@ def group_pairs(pairs: Sequence[tuple[str, str]]) -> list[tuple[str, list[str]]]
 def method_table(pairs: Sequence[tuple[str, str]], methods: Sequence[DistanceMethod], genomes: Mapping[str, Genome],
                  out: TextIO, stats: TextIO | None = None,
                  previous: Mapping[tuple[str, str], Sequence[float]] | None = None,
-                 threads: int = 0, batch: bool = True) -> dict:
+                 threads: int = 0, batch: bool = True, whole_list: bool = False) -> dict:
     """runPipeline (MethodTableProcessor.java:234-308). `genomes` is the
     genome source (id -> Genome); `previous` the map load_previous returns.
     Per pair the methods run concurrently (:275, one thread per method);
     with batch=True each method first prefetches its id1 group in one
-    device row query. Returns counters (pairs, computed, reused)."""
+    device row query. With whole_list=True each method instead packs every
+    genome of the list once and answers all pairs not in `previous` with ONE
+    pair-list call (pair_distances) before the loop, which then only reads; the
+    output is the same bytes. Returns counters (pairs, computed, reused; with
+    whole_list also device_calls, the pair-list calls made)."""
     missing = sorted({x for p in pairs for x in p if x not in genomes})
     if missing:                                        # checkGenomes (:426-433)
         raise IOError("The following genomes are missing from the sources: " + ", ".join(missing))
@@ -292,12 +316,22 @@ def method_table(pairs: Sequence[tuple[str, str]], methods: Sequence[DistanceMet
     counts = {"pairs": 0, "computed": 0, "reused": 0}
     pool = cf.ThreadPoolExecutor(max(1, threads or nm))
     try:
+        whole: list[dict[tuple[str, str], float]] = []
+        if whole_list:
+            keys = list(dict.fromkeys(p for p in pairs if previous is None or p not in previous))
+            gp = [(genomes[a], genomes[b]) for a, b in keys]
+            if keys:
+                whole = [dict(zip(keys, d)) for d in pool.map(lambda m: m.pair_distances(gp), methods)]
+            counts["device_calls"] = nm if keys else 0
         for id1, ids2 in group_pairs(pairs):
             g1 = genomes[id1]
             measurers = [m.getMeasurer(g1) for m in methods]          # getMeasurers (:397-407)
             a1 = TaxonDistanceMethod.Analysis(g1)
             todo = [genomes[b] for b in ids2 if previous is None or (id1, b) not in previous]
-            if batch and todo:
+            if whole_list and todo:
+                for i in range(nm):
+                    measurers[i]._row.update({g.id: whole[i][(id1, g.id)] for g in todo})
+            elif batch and todo:
                 list(pool.map(lambda i: methods[i].prefetch(measurers[i], todo), range(nm)))
             for id2 in ids2:
                 g2 = genomes[id2]

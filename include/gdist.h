@@ -29,6 +29,8 @@
  *                          --maxDist of the genomes table        GenomeProcessor.java:58-60,89
  *   gdist_within           the documented -m filter of the table GenomeProcessor.java:35
  *                          (every pair with d <= maxDist)
+ *   gdist_pairs            getDistance over an (id1, id2) list   MethodTableProcessor.java:258-276
+ *                          the lists of the pairs commands       BasicPairsProcessor.java:71-89, PairCreateProcessor.java:29-32
  *   gdist_group_stats      recordDistance over a distance table  GroupTypeSpec.java:77-95
  *                          in / out-group min, mean, sd, max     DistanceCheckProcessor.java:200-223
  *   gdist_sets_allgather   (new) RCCL all-gather of packed sets for row-sharded N×N
@@ -510,6 +512,35 @@ int  gdist_within(gdist_ctx* ctx, const gdist_sets* sets,
  * made with option "time_kernels" = 1: the matrix kernels and the count, scan
  * and write kernels apart; -1 when the call was not timed. */
 int  gdist_ctx_within_timing(gdist_ctx* ctx, double* matrix_ms, double* select_ms);
+
+/* ---- distances of a pair list ------------------------------------------ */
+/* getDistance over a pair list (MethodTableProcessor.java:258-276): for p in [0, npairs)
+ * I_out[p] = |A_rows[p] ∩ A_cols[p]|, D_out[p] = the distance, host arrays, either may be NULL.
+ *
+ * The list may come in any order, may repeat a pair and may hold i == j:
+ * output slot p depends on (rows[p], cols[p]) only, not on the order, the rest
+ * of the list, the method or the run. D_out[p] is bit for bit the D that
+ * gdist_intersect_matrix writes for that cell with the same flags
+ * (GDIST_EMPTY_NAN is honoured) and I_out[p] its I; for i == j that is |A_i|
+ * (not the popcount of the pruned bitsets) and d = 0.0, or the empty-set value.
+ * method AUTO / SORTED / BITSET is resolved as gdist_closest resolves it, for
+ * npairs pairs; a collection whose codes were released answers BITSET and AUTO.
+ *
+ * The list is uploaded once, sorted by row on the device and cut into work
+ * units there (a row, at most 64 of its pairs, a range of the sorted join's
+ * segment index: a few pairs of huge sets are cut into many units whose
+ * integer counts are added, which is exact); the outputs come back in one
+ * download. npairs == 0: GDIST_OK, nothing is touched. EINVAL, decided before
+ * any work (the outputs stay untouched): npairs < 0 or >= 2^31, null rows or
+ * cols or both outputs null with npairs > 0, an index outside [0, nsets), a
+ * GDIST_SKETCH collection, GDIST_UPPER_TRIANGLE or GDIST_OUT_DEVICE, an
+ * unknown method, SORTED on a bitsets-only collection. */
+int  gdist_pairs(gdist_ctx* ctx, const gdist_sets* sets, int64_t npairs,
+                 const int64_t* rows, const int64_t* cols, int method, unsigned flags,
+                 int32_t* I_out, double* D_out);
+/* last gdist_pairs call: kernel time (ms; -1 unless option "time_kernels" = 1), the
+ * distinct-row groups of the list and the work units launched for them */
+int  gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, int64_t* units);
 
 /* ---- multi-GPU (RCCL over xGMI) -------------------------------------- */
 #define GDIST_UNIQUE_ID_BYTES 128

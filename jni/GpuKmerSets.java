@@ -33,6 +33,8 @@ public final class GpuKmerSets implements AutoCloseable {
     static native boolean nAnyLe(long ctx, long sets, long q, long[] cols, double t);
     static native int nArgmin(long ctx, long sets, long q, long[] cols, double[] bestD);
     static native void nRow(long ctx, long sets, long q, long[] cols, double[] out);
+    static native void nPairs(long ctx, long sets, long[] rows, long[] cols, int method, int flags, int[] I,
+                              double[] D);
     static native long nGreedyReps(long ctx, long sets, double t, long[] tieRank, int[] isRep, long[] repOf,
                                    double[] repDist);
     static native long nSketch(long ctx, long sets, int width);
@@ -105,6 +107,14 @@ public final class GpuKmerSets implements AutoCloseable {
 
     /** the distances of set q to cols */
     public void row(long q, long[] cols, double[] out) { nRow(ctx, handle, q, cols, out); }
+
+    /** getDistance over a pair list (MethodTableProcessor.java:258-276; gdist_pairs) in one
+     *  device call: I[p] = the kmers sets rows[p] and cols[p] share, D[p] = their distance
+     *  (the bits distances() writes for that cell). Any order, repeats and rows[p] == cols[p]
+     *  allowed; either output may be null. */
+    public void pairs(long[] rows, long[] cols, int[] I, double[] D) {
+        nPairs(ctx, handle, rows, cols, METHOD_AUTO, 0, I, D);
+    }
 
     /** argmin over cols (DistanceRepsProcessor.java:238-239): the position in cols,
      *  -1 when none is below 1.0; bestD[0] = its distance */

@@ -263,6 +263,35 @@ JNIEXPORT void JNICALL JFN(nRow)(JNIEnv* env, jclass c, jlong ctx, jlong sets, j
     if (rc) throw_for(env, rc);
 }
 
+/* getDistance over a pair list (MethodTableProcessor.java:258-276): I[p], D[p] of
+ * sets (rows[p], cols[p]); either output array may be null */
+JNIEXPORT void JNICALL JFN(nPairs)(JNIEnv* env, jclass c, jlong ctx, jlong sets, jlongArray rows, jlongArray cols,
+                                   jint method, jint flags, jintArray I, jdoubleArray D) {
+    if (!rows || !cols) { throw_arg(env, "null rows or cols"); return; }
+    jsize n = 0, nc = 0;
+    int64_t* rw = copy_cols(env, rows, &n);
+    if (!rw) return;
+    int64_t* cl = copy_cols(env, cols, &nc);
+    if (!cl) { free(rw); return; }
+    if (nc != n) { free(rw); free(cl); throw_arg(env, "rows and cols differ in length"); return; }
+    if ((!I && !D) || (I && too_short(env, I, n, "I shorter than the pair list")) ||
+        (D && too_short(env, D, n, "D shorter than the pair list"))) {
+        if (!I && !D) throw_arg(env, "both outputs null");
+        free(rw); free(cl);
+        return;
+    }
+    int32_t* vi = I ? malloc(((size_t)n + 1) * sizeof(int32_t)) : NULL;
+    double* vd = D ? malloc(((size_t)n + 1) * sizeof(double)) : NULL;
+    if ((I && !vi) || (D && !vd)) { free(rw); free(cl); free(vi); free(vd); throw_oom(env); return; }
+    int rc = gdist_pairs(CTX(ctx), SETS(sets), n, rw, cl, method, (unsigned)flags, vi, vd);
+    if (!rc && n) {
+        if (vi) (*env)->SetIntArrayRegion(env, I, 0, n, (const jint*)vi);
+        if (vd) (*env)->SetDoubleArrayRegion(env, D, 0, n, vd);
+    }
+    free(rw); free(cl); free(vi); free(vd);
+    if (rc) throw_for(env, rc);
+}
+
 /* greedy representatives, both passes (DistanceRepsProcessor.java:185-262) */
 JNIEXPORT jlong JNICALL JFN(nGreedyReps)(JNIEnv* env, jclass c, jlong ctx, jlong sets, jdouble t,
                                          jlongArray tieRank, jintArray isRep, jlongArray repOf,
