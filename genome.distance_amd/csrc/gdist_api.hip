@@ -1590,6 +1590,60 @@ int gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, int
     });
 }
 
+// ---------------------------------------------------------------------------
+int gdist_histogram(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, int64_t r1, int64_t c0, int64_t c1,
+                    int method, unsigned flags, int nedges, const double* edges, int ntypes, const int32_t* labels,
+                    int64_t* counts_out, int64_t* nans_out, int64_t* bad_out) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_sets(sets);
+        GD_REQUIRE(sets->ctx == ctx, "sets belong to another context");
+        GD_REQUIRE(0 <= r0 && r0 <= r1 && r1 <= sets->nsets && 0 <= c0 && c0 <= c1 && c1 <= sets->nsets,
+                   "row/column range outside the set collection");
+        GD_REQUIRE(nedges >= 1 && nedges <= GDIST_HIST_MAX_EDGES, "nedges outside 1 .. GDIST_HIST_MAX_EDGES");
+        GD_REQUIRE(ntypes >= 0 && ntypes <= GDIST_GROUP_MAX_TYPES, "ntypes outside 0 .. GDIST_GROUP_MAX_TYPES");
+        GD_REQUIRE(edges && counts_out && nans_out, "null edges or output");
+        GD_REQUIRE(ntypes == 0 || (labels && bad_out), "null labels or bad_out with ntypes > 0");
+        GD_REQUIRE(!(flags & GDIST_OUT_DEVICE), "gdist_histogram does not support GDIST_OUT_DEVICE");
+        for (int e = 0; e < nedges; e++) {
+            GD_REQUIRE(edges[e] == edges[e], "an edge is NaN");
+            // -0.0 == 0.0: a signed-zero pair is not ascending either
+            GD_REQUIRE(e == 0 || edges[e - 1] < edges[e], "edges are not strictly ascending");
+        }
+        const bool sketch = sets->kind == GDIST_SKETCH;
+        if (sketch) {
+            check_codes(sets);
+        } else {
+            GD_REQUIRE(method >= GDIST_METHOD_AUTO && method <= GDIST_METHOD_BITSET, "unknown method");
+            GD_REQUIRE(method != GDIST_METHOD_SORTED || sets->has_codes, "this collection holds bitsets only");
+        }
+        const int64_t nr = r1 - r0, nc = c1 - c0;
+        auto* s = const_cast<gdist_sets*>(sets);
+        int m = GDIST_METHOD_AUTO;
+        if (!sketch && nr > 0 && nc > 0) m = resolve_method(ctx, s, method, (double)nr * (double)nc);
+        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
+        ctx->last = Timing{};
+        // into locals first: a failure on the device leaves the outputs untouched too
+        const size_t series = ntypes ? (size_t)2 * ntypes : 1;
+        std::vector<int64_t> cn(series * ((size_t)nedges + 1)), na(series), b((size_t)ntypes);
+        gdist::histogram(ctx, s, r0, r1, c0, c1, m, flags, nedges, edges, ntypes, labels, cn.data(), na.data(),
+                         b.data());
+        std::copy(cn.begin(), cn.end(), counts_out);
+        std::copy(na.begin(), na.end(), nans_out);
+        if (ntypes) std::copy(b.begin(), b.end(), bad_out);
+    });
+}
+
+int gdist_ctx_histogram_timing(gdist_ctx* ctx, double* matrix_ms, double* reduce_ms) {
+    return guard([&] {
+        GD_REQUIRE(ctx != nullptr, "null context");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        if (matrix_ms) *matrix_ms = ctx->hist_matrix_ms;
+        if (reduce_ms) *reduce_ms = ctx->hist_reduce_ms;
+    });
+}
+
 int gdist_comm_unique_id(char id[GDIST_UNIQUE_ID_BYTES]) {
     return guard([&] {
         static_assert(sizeof(ncclUniqueId) <= GDIST_UNIQUE_ID_BYTES, "unique id size");

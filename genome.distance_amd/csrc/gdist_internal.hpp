@@ -347,6 +347,8 @@ struct gdist_ctx {
     double group_matrix_ms = -1.0, group_reduce_ms = -1.0;
     // the same for the last gdist_within call: matrix kernels, count + scan + write kernels
     double within_matrix_ms = -1.0, within_select_ms = -1.0;
+    // the same for the last gdist_histogram call: matrix kernels, histogram kernel
+    double hist_matrix_ms = -1.0, hist_reduce_ms = -1.0;
     // the last gdist_pairs call: its kernels' time (option time_kernels = 1, else -1),
     // the distinct-row groups of its list and the work units launched for them
     double pairs_kernel_ms = -1.0;
@@ -731,6 +733,15 @@ void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t 
 int64_t within_rows(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem);
 void within(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
             unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr, int64_t* col_out, double* d_out);
+
+// hist.hip — distribution of the distances over bucket edges (gdist_histogram)
+// method: SORTED or BITSET (resolved by the caller, every argument checked);
+// ignored for sketches. edges: host, nedges ascending values; labels: host,
+// [ntypes][nsets], null when ntypes == 0. counts: [S][nedges + 1], nans: [S]
+// (S = 1 without labels, else 2 ntypes), bad: [ntypes]; written whole
+void histogram(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
+               unsigned flags, int nedges, const double* edges, int ntypes, const int32_t* labels, int64_t* counts,
+               int64_t* nans, int64_t* bad);
 
 // pairs.hip — the distances of a pair list (gdist_pairs)
 // method: SORTED or BITSET (resolved by the caller, every argument checked);

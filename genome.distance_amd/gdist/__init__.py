@@ -6,12 +6,12 @@ loudly if it is missing: there is no CPU fallback on the product path.
 """
 from . import _lib
 from ._lib import (AMBIG_DEFAULT, AMBIG_KEEP, AMBIG_SKIP, BITSET_KEEP_SINGLETONS, CLOSEST_KEEP_SELF, CLOSEST_MAX_N,
-                   EMPTY_NAN, GROUP_MAX_TYPES, METHOD_AUTO,
+                   EMPTY_NAN, GROUP_MAX_TYPES, HIST_MAX_EDGES, METHOD_AUTO,
                    METHOD_BITSET, METHOD_SORTED, NO_CASE_FOLD, QUERY_ALL, QUERY_ANY_LE, QUERY_ARGMIN,
                    SKETCH_JACCARD, STRAND_BOTH, STRAND_CANON, STRAND_FWD, UPPER_TRIANGLE, GdistError)
 from .fasta import Sequence, read_fasta, write_fasta
 from .javafmt import java_double, java_doubles
-from .kmers import (Context, DeviceBuffer, GroupStats, HostBuffer, release_device_cache, KmerSets, KmerType, LSHIndex, SequenceKmers, SketchSets, option_names,
+from .kmers import (Context, DeviceBuffer, GroupStats, Histogram, HostBuffer, release_device_cache, KmerSets, KmerType, LSHIndex, SequenceKmers, SketchSets, option_names,
                     options_from_env, triangle_partition)
 
 __version__ = _lib.lib.gdist_version().decode()

@@ -25,6 +25,7 @@ ALLGATHER_CONSUME = 0x1
 QUERY_ALL, QUERY_ANY_LE, QUERY_ARGMIN = 0, 1, 2
 CLOSEST_KEEP_SELF, CLOSEST_MAX_N = 0x1000, 512
 GROUP_MAX_TYPES = 8
+HIST_MAX_EDGES = 1023
 UNIQUE_ID_BYTES = 128
 OPTION_DEFAULT = -(1 << 63)   # GDIST_OPTION_DEFAULT
 
@@ -155,6 +156,9 @@ _SIGS = {
     "gdist_ctx_within_timing": (C.c_int, [_ctxp, _dblp, _dblp]),
     "gdist_pairs": (C.c_int, [_ctxp, _setp, _i64, _i64p, _i64p, C.c_int, _u32, _i32p, _dblp]),
     "gdist_ctx_pairs_info": (C.c_int, [_ctxp, _dblp, _i64p, _i64p]),
+    "gdist_histogram": (C.c_int, [_ctxp, _setp, _i64, _i64, _i64, _i64, C.c_int, _u32, C.c_int, _dblp, C.c_int, _i32p,
+                                  _i64p, _i64p, _i64p]),
+    "gdist_ctx_histogram_timing": (C.c_int, [_ctxp, _dblp, _dblp]),
     "gdist_comm_unique_id": (C.c_int, [C.c_char_p]),
     "gdist_comm_init": (C.c_int, [_ctxp, C.c_char_p, C.c_int, C.c_int]),
     "gdist_comm_init_host": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_void_p, _vp]),

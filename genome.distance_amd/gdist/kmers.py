@@ -17,6 +17,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import enum
+import math
 import os
 import weakref
 from typing import Iterable, Mapping, Sequence
@@ -139,6 +140,13 @@ class Context:
         (-1: not timed)."""
         m, s = C.c_double(), C.c_double()
         L.check(L.lib.gdist_ctx_within_timing(self.h, C.byref(m), C.byref(s)))
+        return m.value, s.value
+
+    def histogram_timing(self) -> tuple[float, float]:
+        """(matrix kernels ms, histogram kernel ms) of the last histogram() call
+        made with option time_kernels = 1, summed over its steps (-1: not timed)."""
+        m, s = C.c_double(), C.c_double()
+        L.check(L.lib.gdist_ctx_histogram_timing(self.h, C.byref(m), C.byref(s)))
         return m.value, s.value
 
     def recent_timings(self, n: int) -> list[float]:
@@ -363,6 +371,46 @@ class GroupStats:
         return self.mean + self.sdev
 
 
+class Histogram:
+    """Result of histogram (gdist_histogram): how the distances of a region are
+    distributed over E ascending bucket edges.
+
+    edges: float64 [E]; counts: int64 [S, E + 1], counts[s, b] the pairs of
+    series s with edges[b - 1] <= d < edges[b] (bucket 0: d < edges[0], bucket
+    E: d >= edges[E - 1]); nans: int64 [S], the NaN pairs, in no bucket; bad:
+    int64 [T], pairs with an unlabelled set. Without labels S = 1 and T = 0;
+    with T groupings S = 2 T, series 2 t in-group and 2 t + 1 out-group.
+    Every field is an exact integer count: histograms of disjoint regions with
+    the same edges and labels add (`a + b`)."""
+
+    def __init__(self, edges, counts, nans, bad):
+        self.edges = np.ascontiguousarray(edges, dtype=np.float64)
+        self.counts = np.ascontiguousarray(counts, dtype=np.int64)
+        self.nans = np.ascontiguousarray(nans, dtype=np.int64)
+        self.bad = np.ascontiguousarray(bad, dtype=np.int64)
+
+    @property
+    def total(self) -> np.ndarray:
+        """int64 [S]: the pairs of every series (all buckets and the NaNs)."""
+        return self.counts.sum(axis=1) + self.nans
+
+    def tobytes(self) -> bytes:
+        """counts, nans and bad as the library wrote them."""
+        return self.counts.tobytes() + self.nans.tobytes() + self.bad.tobytes()
+
+    def __add__(self, other: "Histogram") -> "Histogram":
+        if not isinstance(other, Histogram):
+            return NotImplemented
+        if self.edges.tobytes() != other.edges.tobytes():
+            raise ValueError("histograms over different edges")
+        if self.counts.shape != other.counts.shape or self.bad.shape != other.bad.shape:
+            raise ValueError("histograms of different shapes")
+        return Histogram(self.edges, self.counts + other.counts, self.nans + other.nans, self.bad + other.bad)
+
+
+_BITS_ONE = 0x3FF0000000000000      # the pattern of 1.0: d >= 0 is ordered by its unsigned pattern
+
+
 class _Handle:
     def __init__(self, ctx: Context, h: C.c_void_p):
         self.ctx, self.h = ctx, h
@@ -423,6 +471,86 @@ class _Handle:
         L.check(L.lib.gdist_group_stats(self.ctx.h, self.h, r0, r1, c0, c1, method, fl, T, L.ptr(buf, C.c_int32),
                                         C.addressof(sides), bad))
         return GroupStats(sides, bad)
+
+    def _histogram(self, edges, labels, rows, cols, upper: bool, method: int, flags: int) -> Histogram:
+        ns = len(self)
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        if not 1 <= len(e) <= L.HIST_MAX_EDGES:
+            raise ValueError(f"{len(e)} edges: 1 .. {L.HIST_MAX_EDGES} a call")
+        if labels is None:
+            lab, T = None, 0
+        else:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.ndim == 1:
+                lab = lab[None, :]
+            if lab.ndim != 2 or lab.shape[1] != ns:
+                raise ValueError(f"labels must be [T, {ns}] or [{ns}], not {list(lab.shape)}")
+            T = lab.shape[0]
+            if not 1 <= T <= L.GROUP_MAX_TYPES:
+                raise ValueError(f"{T} groupings: 1 .. {L.GROUP_MAX_TYPES} a call")
+            if not lab.size:
+                lab = np.zeros((T, 1), dtype=np.int32)
+        r0, r1 = rows or (0, ns)
+        c0, c1 = cols or (0, ns)
+        S = 2 * T if T else 1
+        counts = np.zeros((S, len(e) + 1), dtype=np.int64)
+        nans = np.zeros(S, dtype=np.int64)
+        bad = np.zeros(max(T, 1), dtype=np.int64)
+        fl = flags | (L.UPPER_TRIANGLE if upper else 0)
+        L.check(L.lib.gdist_histogram(self.ctx.h, self.h, r0, r1, c0, c1, method, fl, len(e), L.ptr(e, C.c_double),
+                                      T, L.ptr(lab, C.c_int32) if T else None, L.ptr(counts, C.c_int64),
+                                      L.ptr(nans, C.c_int64), L.ptr(bad, C.c_int64) if T else None))
+        return Histogram(e, counts, nans, bad[:T])
+
+    def _quantiles(self, q, rows, cols, upper: bool, method: int, flags: int):
+        """Exact order statistics from histogram calls alone. d >= 0 and never
+        -0.0, so its unsigned bit pattern orders it: per quantile an inclusive
+        pattern interval [lo, hi] that holds the value of rank k. Every call
+        cuts each unfinished interval into equal pattern ranges with its share
+        of the 1023 edges and keeps the range that holds rank k (the counts
+        below every edge are the cumulative sums of the buckets)."""
+        qs = np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1)
+        if len(qs) > 8:
+            raise ValueError(f"{len(qs)} quantiles: at most 8 a call")
+        if len(qs) and not np.all((qs >= 0.0) & (qs <= 1.0)):     # NaN fails too
+            raise ValueError("a quantile outside [0, 1]")
+        out = np.full(len(qs), np.nan, dtype=np.float64)
+        if not len(qs):
+            return out, 0, 0
+        # invariant per quantile: fewer than k values lie below lo, at least k at or below hi
+        iv = [[0, _BITS_ONE] for _ in qs]
+        rank, n, calls = None, 0, 0
+        while any(lo < hi for lo, hi in iv):
+            # distinct unfinished intervals (in the first call all are one: [0.0, 1.0])
+            todo = sorted({(lo, hi) for lo, hi in iv if lo < hi})
+            share = L.HIST_MAX_EDGES // len(todo)
+            pats = set()
+            for lo, hi in todo:
+                m = hi - lo + 1                       # patterns; pieces of at most ceil(m / (share + 1))
+                pieces = min(m, share + 1)
+                pats.update(lo + (i * m + pieces - 1) // pieces for i in range(1, pieces))
+            pats = np.array(sorted(pats), dtype=np.uint64)
+            h = self._histogram(pats.view(np.float64), None, rows, cols, upper, method, flags)
+            calls += 1
+            below = np.cumsum(h.counts[0])            # below[i]: values < edge i (NaN is in no bucket)
+            if rank is None:
+                n = int(below[-1])
+                if n == 0:
+                    return out, 0, calls
+                rank = [max(1, min(n, int(math.ceil(float(x) * n)))) for x in qs]
+            for v, k in zip(iv, rank):
+                lo, hi = v
+                if lo == hi:
+                    continue
+                # edges a .. b - 1 lie in (lo, hi]; i: the first of them with at least k values below it
+                a = int(np.searchsorted(pats, np.uint64(lo), side="right"))
+                b = int(np.searchsorted(pats, np.uint64(hi), side="right"))
+                i = a + int(np.searchsorted(below[a:b], k, side="left"))
+                if i > a:
+                    v[0] = int(pats[i - 1])
+                if i < b:
+                    v[1] = int(pats[i]) - 1
+        return np.array([lo for lo, _ in iv], dtype=np.uint64).view(np.float64), n, calls
 
     # first capacity guess of within(capacity=None): entries a row of the call
     WITHIN_GUESS_PER_ROW = 64
@@ -767,6 +895,27 @@ class KmerSets(_Handle):
         exact, so the result does not depend on method or block sizes."""
         return self._group_stats(labels, rows, cols, upper, method, flags)
 
+    def histogram(self, edges, labels=None, rows: tuple[int, int] | None = None,
+                  cols: tuple[int, int] | None = None, upper: bool = True, method: int = L.METHOD_AUTO,
+                  flags: int = 0) -> Histogram:
+        """How the distances of rows x cols are distributed (gdist_histogram):
+        edges float64 [E], strictly ascending, at most HIST_MAX_EDGES; a
+        distance goes to bucket numpy.searchsorted(edges, d, "right"), NaN to
+        `nans`. labels None: one series of every pair; int32 [T, N] or [N]:
+        per grouping an in-group and an out-group series, split as group_stats
+        splits them. upper: only the pairs j > i. The distances are matrix()'s
+        D bit for bit and never leave the device; every count is exact."""
+        return self._histogram(edges, labels, rows, cols, upper, method, flags)
+
+    def quantiles(self, q, rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,
+                  upper: bool = True, method: int = L.METHOD_AUTO, flags: int = 0):
+        """Exact order statistics of the non-NaN distances of rows x cols, from
+        a few histogram() calls: (values float64 [len(q)], n, calls). With the
+        n values sorted ascending as x_1..x_n the value for q in [0, 1] is x_k,
+        k = max(1, min(n, ceil(q n))); n == 0 gives NaN. At most 8 quantiles a
+        call: one finishes in at most 7 histogram calls, eight in at most 9."""
+        return self._quantiles(q, rows, cols, upper, method, flags)
+
     def pairs(self, rows, cols, method: int = L.METHOD_AUTO, flags: int = 0, want_I: bool = True,
               want_D: bool = True):
         """Distances of a pair list (gdist_pairs): for every p the intersection
@@ -912,6 +1061,19 @@ class SketchSets(_Handle):
         """In-group / out-group summary of the sketch distances (gdist_group_stats;
         flags: SKETCH_JACCARD, EMPTY_NAN; method is ignored): as KmerSets.group_stats."""
         return self._group_stats(labels, rows, cols, upper, L.METHOD_AUTO, flags)
+
+    def histogram(self, edges, labels=None, rows: tuple[int, int] | None = None,
+                  cols: tuple[int, int] | None = None, upper: bool = True, method: int = L.METHOD_AUTO,
+                  flags: int = 0) -> Histogram:
+        """How the sketch distances are distributed (gdist_histogram; flags:
+        SKETCH_JACCARD, EMPTY_NAN; method is ignored): as KmerSets.histogram."""
+        return self._histogram(edges, labels, rows, cols, upper, L.METHOD_AUTO, flags)
+
+    def quantiles(self, q, rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,
+                  upper: bool = True, method: int = L.METHOD_AUTO, flags: int = 0):
+        """Exact order statistics of the sketch distances (flags: SKETCH_JACCARD,
+        EMPTY_NAN; method is ignored): as KmerSets.quantiles."""
+        return self._quantiles(q, rows, cols, upper, L.METHOD_AUTO, flags)
 
     def matrix_device(self, d_common: int | None, d_D: int | None, ld: int, rows, cols, upper=False, flags=0):
         fl = flags | L.OUT_DEVICE | (L.UPPER_TRIANGLE if upper else 0)

@@ -459,3 +459,36 @@ def distance_check(sets, ids: Sequence[str], groupings: dict, out: TextIO, name:
         raise ValueError(f"{len(ids)} ids for {len(sets)} sets")
     names, lab = group_labels(ids, groupings)
     return write_distance_check(sets.group_stats(lab, **kw), names, out, name, header)
+
+
+def distance_distribution(sets, ids: Sequence[str], groupings: dict, out: TextIO, name: str, buckets: int = 50,
+                          header: bool = True, **kw) -> int:
+    """The --dist companion of distance_check: how the in-group and out-group
+    distances of every grouping are distributed over `buckets` equal buckets of
+    [0, 1] (TaxCheckProcessor.java:93 sets up 50 of them,
+    TaxCheckProcessor.java:133-135 feeds every series of distances in), from
+    one histogram call over a device-resident collection. The edges are
+    i / buckets, i = 0..buckets; one row per (grouping, in / out, bucket) with
+    the columns dist_file, group_type, in_out, low, high, count: the bucket
+    low <= d < high, doubles as Java prints them. The last row of a series is
+    d >= 1.0 and has `high` empty; d < 0.0 never occurs and has no row; NaN
+    distances are in no bucket. The reference writes its buckets to an Excel
+    sheet, this writes the same counts as a table. **kw goes to histogram
+    (rows, cols, upper, method, flags; by default the pairs j > i). Returns
+    the bad pairs."""
+    if len(ids) != len(sets):
+        raise ValueError(f"{len(ids)} ids for {len(sets)} sets")
+    if not 1 <= buckets <= 1022:
+        raise ValueError(f"{buckets} buckets: 1 .. 1022")
+    names, lab = group_labels(ids, groupings)
+    edges = np.array([i / buckets for i in range(buckets + 1)], dtype=np.float64)
+    hist = sets.histogram(edges, lab, **kw)
+    if header:
+        out.write("dist_file\tgroup_type\tin_out\tlow\thigh\tcount\n")
+    for t, gtype in enumerate(names):
+        for k, side in enumerate(("in", "out")):
+            for b in range(1, len(edges) + 1):
+                high = java_double(float(edges[b])) if b < len(edges) else ""
+                cells = [name, gtype, side, java_double(float(edges[b - 1])), high, str(int(hist.counts[2 * t + k, b]))]
+                out.write("\t".join(cells) + "\n")
+    return int(hist.bad.sum())

@@ -33,6 +33,10 @@
  *                          the lists of the pairs commands       BasicPairsProcessor.java:71-89, PairCreateProcessor.java:29-32
  *   gdist_group_stats      recordDistance over a distance table  GroupTypeSpec.java:77-95
  *                          in / out-group min, mean, sd, max     DistanceCheckProcessor.java:200-223
+ *   gdist_histogram        new Distributor(0.0, 1.0, 50)         TaxCheckProcessor.java:93
+ *                          fed every (method; group) series      TaxCheckProcessor.java:133-135
+ *                          the count of pairs with d < 1.0       WidthProcessor.java:162
+ *                          the close pairs below the target      TuningProcessor.java:131-133
  *   gdist_sets_allgather   (new) RCCL all-gather of packed sets for row-sharded N×N
  *
  * Kmer code spec (shared by the device packer, the CPU oracle in oracle/ and
@@ -541,6 +545,66 @@ int  gdist_pairs(gdist_ctx* ctx, const gdist_sets* sets, int64_t npairs,
 /* last gdist_pairs call: kernel time (ms; -1 unless option "time_kernels" = 1), the
  * distinct-row groups of the list and the work units launched for them */
 int  gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, int64_t* units);
+
+/* ---- distribution of the distances ------------------------------------- */
+/* How the distances of a rectangle are distributed over caller-supplied
+ * bucket edges, without the distance table leaving the device: the bucket
+ * report of the taxonomy check (TaxCheckProcessor.java:93 sets up 50 buckets
+ * over [0, 1], TaxCheckProcessor.java:133-135 feeds every series into them),
+ * and what a max_dist for gdist_within, gdist_closest or gdist_greedy_reps is
+ * chosen from. A histogram also answers the hand-rolled counts of the
+ * reference (pairs with d < 1.0, WidthProcessor.java:162; close pairs below a
+ * target, TuningProcessor.java:131-133) and any multi-threshold count.
+ *
+ * Pairs are those of gdist_group_stats: (i, j), i in [r0, r1), j in [c0, c1);
+ * with GDIST_UPPER_TRIANGLE only j > i counts, without it a diagonal pair
+ * inside the rectangle counts like any other. d is the bit pattern
+ * gdist_intersect_matrix (kmer sets; method AUTO / SORTED / BITSET resolved
+ * as gdist_closest resolves it) or gdist_sketch_matrix (GDIST_SKETCH
+ * collections: method ignored) writes with the same flags (GDIST_EMPTY_NAN,
+ * GDIST_SKETCH_JACCARD).
+ *
+ * Series. ntypes == 0: one series (S = 1) of every pair; labels and bad_out
+ * may be NULL. ntypes in 1..GDIST_GROUP_MAX_TYPES: S = 2 ntypes, series 2 t
+ * the in-group and 2 t + 1 the out-group pairs of grouping t, split as
+ * gdist_group_stats splits them (GroupTypeSpec.java:77-95): a label < 0 on
+ * either set adds 1 to bad_out[t] and nothing else.
+ *
+ * Buckets. With edges e_0 < ... < e_{E-1} (host, strictly ascending; -inf and
+ * +inf allowed) a non-NaN d goes to bucket b = the number of edges <= d
+ * (numpy.searchsorted(edges, d, side="right")): bucket 0 is d < e_0, bucket b
+ * is e_{b-1} <= d < e_b, bucket E is d >= e_{E-1}. The bucket is found by
+ * fp64 comparisons against the edges alone, so edges one ulp apart and
+ * denormal edges are exact. d == 1.0 is bucketed like any other value: an
+ * edge at 1.0 separates the "ones". NaN goes to nans_out[s] and to no bucket,
+ * so for every series sum_b counts + nans is its number of pairs (with
+ * ntypes >= 1: n + ones + nans of the matching gdist_group_side).
+ * counts_out[s * (E + 1) + b], nans_out[s]. The reference's buckets are the
+ * edges i / 50, i = 0..50.
+ *
+ * Every output is an integer count decided by fp64 comparisons, so the result
+ * does not depend on block sizes, method, pair order, run or rank, and the
+ * results of disjoint rectangles with the same edges and labels add
+ * element-wise (no merge call). The walk is gdist_group_stats's (options
+ * "closest_rows" / "closest_cols"). An empty row or column range: GDIST_OK,
+ * every output zero. EINVAL, decided before any work (the outputs stay
+ * untouched): a bad range, nedges outside 1..GDIST_HIST_MAX_EDGES, a NaN
+ * edge, edges not strictly ascending (-0.0 next to 0.0 is not), ntypes
+ * outside 0..GDIST_GROUP_MAX_TYPES, null edges, counts_out or nans_out, null
+ * labels or bad_out with ntypes > 0, GDIST_OUT_DEVICE, an unknown method,
+ * SORTED on a bitsets-only collection. */
+#define GDIST_HIST_MAX_EDGES 1023          /* at most 1024 buckets */
+int  gdist_histogram(gdist_ctx* ctx, const gdist_sets* sets,
+                     int64_t r0, int64_t r1, int64_t c0, int64_t c1,
+                     int method, unsigned flags,
+                     int nedges, const double* edges /* host, strictly ascending */,
+                     int ntypes, const int32_t* labels /* [ntypes][nsets], host; NULL when ntypes == 0 */,
+                     int64_t* counts_out /* [S][nedges + 1] */, int64_t* nans_out /* [S] */,
+                     int64_t* bad_out /* [ntypes]; may be NULL when ntypes == 0 */);
+/* HIP-event time (ms, summed over the steps) of the last gdist_histogram call
+ * made with option "time_kernels" = 1: the matrix kernels and the histogram
+ * kernel apart; -1 when the call was not timed. */
+int  gdist_ctx_histogram_timing(gdist_ctx* ctx, double* matrix_ms, double* reduce_ms);
 
 /* ---- multi-GPU (RCCL over xGMI) -------------------------------------- */
 #define GDIST_UNIQUE_ID_BYTES 128
