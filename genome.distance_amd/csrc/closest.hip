@@ -58,13 +58,16 @@ __device__ __forceinline__ void wave_sort(unsigned long long* kd, uint32_t* kc, 
 
 // Rows [q0, q0 + nrows) against the chunk's columns [c0, c0 + nc).
 //  FromCounts: src is I (int32, row a / column b at src[a * ld + b]) and d is
-//  the Java expression of epilogue_kernel (bitset.hip), fp64, no contraction;
+//  the Java expression of epilogue_kernel (bitset.hip), fp64, no contraction,
+//  with the row's size from roff and the column's from coff (one collection:
+//  the same array; gdist_cross_closest: the queries' and the subjects');
 //  else src is D (double, the same layout).
 // State per row: st_n (list length), st_d / st_c (L keys). `last`: write the
 // block's outputs (idx / d: [nrows][n], count: [nrows]).
 template <bool FromCounts>
 __global__ __launch_bounds__(256) void closest_select_kernel(
-    const void* __restrict__ src, int64_t ld, const int64_t* __restrict__ off, int empty_nan, int64_t q0,
+    const void* __restrict__ src, int64_t ld, const int64_t* __restrict__ roff, const int64_t* __restrict__ coff,
+    int empty_nan, int64_t q0,
     int64_t nrows, int64_t c0, int64_t nc, int keep_self, int n, int L, double max_dist,
     unsigned long long* __restrict__ st_d, uint32_t* __restrict__ st_c, int32_t* __restrict__ st_n, int last,
     int64_t* __restrict__ idx_out, double* __restrict__ d_out, int32_t* __restrict__ count_out) {
@@ -90,7 +93,7 @@ __global__ __launch_bounds__(256) void closest_select_kernel(
 
     const int64_t q = q0 + a;
     int64_t na = 0;
-    if (FromCounts) na = off[q + 1] - off[q];
+    if (FromCounts) na = roff[q + 1] - roff[q];
     const int32_t* Ir = static_cast<const int32_t*>(src) + a * ld;
     const double* Dr = static_cast<const double*>(src) + a * ld;
 
@@ -105,7 +108,7 @@ __global__ __launch_bounds__(256) void closest_select_kernel(
                 if (FromCounts) {
                     const int64_t j = c0 + b;
                     const int64_t inter = Ir[b];
-                    const int64_t nb = off[j + 1] - off[j];
+                    const int64_t nb = coff[j + 1] - coff[j];
                     if (inter > 0) {
                         const double uni = (double)(na + nb - inter);
                         d = 1.0 - (double)inter / uni;
@@ -184,6 +187,19 @@ void closest_blocks(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem, i
     *cols = W;
 }
 
+// one select step over counts whose rows and columns come from two collections
+// (cross.hip): every column may be a neighbour (no self to leave out)
+void closest_select_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff,
+                           const int64_t* d_coff, int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc,
+                           int n, int L, double max_dist, unsigned long long* st_d, uint32_t* st_c, int32_t* st_n,
+                           int last, int64_t* d_idx, double* d_d, int32_t* d_count) {
+    const size_t lds = (size_t)4 * 2 * L * 12;
+    closest_select_kernel<true><<<(unsigned)ceil_div(nrows, 4), 256, lds, ctx->stream>>>(
+        d_I, ld, d_roff, d_coff, empty_nan, q0, nrows, c0, nc, 1, n, L, max_dist, st_d, st_c, st_n, last, d_idx, d_d,
+        d_count);
+    GD_HIP(hipGetLastError());
+}
+
 // method: SORTED or BITSET (resolved by the caller); ignored for sketches
 void closest(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
              unsigned flags, int n, double max_dist, int64_t* idx_out, double* d_out, int32_t* count_out) {
@@ -232,12 +248,12 @@ void closest(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, 
             const unsigned grid = (unsigned)ceil_div(nb, 4);
             if (sketch)
                 closest_select_kernel<false><<<grid, 256, lds, st>>>(
-                    blk.p, nk, nullptr, empty_nan, b0, nb, k0, nk, keep_self, n, L, max_dist,
+                    blk.p, nk, nullptr, nullptr, empty_nan, b0, nb, k0, nk, keep_self, n, L, max_dist,
                     sd.as<unsigned long long>(), sc.as<uint32_t>(), sn.as<int32_t>(), last, oi.as<int64_t>(),
                     od.as<double>(), oc.as<int32_t>());
             else
                 closest_select_kernel<true><<<grid, 256, lds, st>>>(
-                    blk.p, nk, s->off.as<int64_t>(), empty_nan, b0, nb, k0, nk, keep_self, n, L, max_dist,
+                    blk.p, nk, s->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan, b0, nb, k0, nk, keep_self, n, L, max_dist,
                     sd.as<unsigned long long>(), sc.as<uint32_t>(), sn.as<int32_t>(), last, oi.as<int64_t>(),
                     od.as<double>(), oc.as<int32_t>());
             GD_HIP(hipGetLastError());

@@ -879,15 +879,21 @@ int gdist_sets_bitset_download(const gdist_sets* s, uint64_t* bits) {
     });
 }
 
+// two collections whose sets may meet (gdist_sets_concat, gdist_cross_*): one
+// context, one kmer spec (GDIST_NO_CASE_FOLD may differ)
+static void check_same_spec(const gdist_sets* a, const gdist_sets* b) {
+    GD_REQUIRE(a->ctx == b->ctx, "sets belong to different contexts");
+    GD_REQUIRE(a->kind == b->kind && a->k == b->k && a->width == b->width &&
+                   (a->flags & ~GDIST_NO_CASE_FOLD) == (b->flags & ~GDIST_NO_CASE_FOLD),
+               "sets were packed with different kmer specs");
+}
+
 int gdist_sets_concat(const gdist_sets* a, const gdist_sets* b, gdist_sets** out) {
     return guard([&] {
         check_codes(a);
         check_codes(b);
         GD_REQUIRE(out, "null output");
-        GD_REQUIRE(a->ctx == b->ctx, "sets belong to different contexts");
-        GD_REQUIRE(a->kind == b->kind && a->k == b->k && a->width == b->width &&
-                       (a->flags & ~GDIST_NO_CASE_FOLD) == (b->flags & ~GDIST_NO_CASE_FOLD),
-                   "sets were packed with different kmer specs");
+        check_same_spec(a, b);
         gdist_ctx* ctx = a->ctx;
         use_device(ctx);
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
@@ -1587,6 +1593,86 @@ int gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, int
         if (kernel_ms) *kernel_ms = ctx->pairs_kernel_ms;
         if (groups) *groups = ctx->pairs_groups;
         if (units) *units = ctx->pairs_units;
+    });
+}
+
+// ---------------------------------------------------------------------------
+// what gdist_cross_matrix and gdist_cross_closest refuse alike, before any work
+static void check_cross(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects, int64_t q0, int64_t q1,
+                        int64_t c0, int64_t c1, unsigned flags) {
+    check_sets(queries);
+    check_sets(subjects);
+    GD_REQUIRE(queries->ctx == ctx && subjects->ctx == ctx, "sets belong to another context");
+    GD_REQUIRE(queries->kind != GDIST_SKETCH && subjects->kind != GDIST_SKETCH,
+               "cross calls run on kmer sets (sketches: gdist_lsh_closest)");
+    check_same_spec(queries, subjects);
+    check_codes(queries);
+    check_codes(subjects);
+    GD_REQUIRE(0 <= q0 && q0 <= q1 && q1 <= queries->nsets, "query range outside the query collection");
+    GD_REQUIRE(0 <= c0 && c0 <= c1 && c1 <= subjects->nsets, "column range outside the subject collection");
+    GD_REQUIRE(!(flags & ~GDIST_EMPTY_NAN), "cross calls take no flag but GDIST_EMPTY_NAN");
+    GD_REQUIRE(subjects->nsets < (int64_t)UINT32_MAX, "too many subjects for 32-bit column keys");
+}
+
+static void begin_cross(gdist_ctx* ctx) {
+    ctx->cross_join_ms = ctx->cross_select_ms = -1.0;
+    ctx->cross_units = 0;
+    ctx->pending = false;          // an unread previous call's times are dropped, not waited for
+    ctx->last = Timing{};
+}
+
+int gdist_cross_matrix(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects, int64_t q0, int64_t q1,
+                       int64_t c0, int64_t c1, unsigned flags, int32_t* I_out, double* D_out, int64_t ld) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_cross(ctx, queries, subjects, q0, q1, c0, c1, flags);
+        const int64_t nr = q1 - q0, nc = c1 - c0;
+        GD_REQUIRE(ld >= nc, "leading dimension smaller than the column range");
+        GD_REQUIRE(nr == 0 || nc == 0 || I_out || D_out, "both outputs null");
+        auto* s = const_cast<gdist_sets*>(subjects);
+        begin_cross(ctx);
+        if (nr == 0 || nc == 0) return;
+        // the one thing a cross call may add to the subjects, as a SORTED call on them does
+        if (!s->segoff.p) build_segments(ctx, s);
+        gdist::cross_matrix(ctx, queries, s, q0, q1, c0, c1, flags, I_out, D_out, ld);
+    });
+}
+
+int gdist_cross_closest(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects, int64_t q0, int64_t q1,
+                        int64_t c0, int64_t c1, unsigned flags, int n, double max_dist, int64_t* idx_out,
+                        double* d_out, int32_t* count_out) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_cross(ctx, queries, subjects, q0, q1, c0, c1, flags);
+        GD_REQUIRE(n >= 0 && n <= GDIST_CLOSEST_MAX_N, "n outside 0 .. GDIST_CLOSEST_MAX_N");
+        GD_REQUIRE(max_dist == max_dist, "max_dist is NaN");
+        const int64_t nr = q1 - q0, nc = c1 - c0;
+        GD_REQUIRE(nr == 0 || (count_out && (n == 0 || (idx_out && d_out))), "null output");
+        auto* s = const_cast<gdist_sets*>(subjects);
+        begin_cross(ctx);
+        if (nr == 0) return;
+        if (n == 0 || nc == 0) {
+            std::fill(count_out, count_out + nr, 0);
+            if (n) {
+                std::fill(idx_out, idx_out + nr * n, (int64_t)-1);
+                std::fill(d_out, d_out + nr * n, 1.0);
+            }
+            return;
+        }
+        if (!s->segoff.p) build_segments(ctx, s);
+        gdist::cross_closest(ctx, queries, s, q0, q1, c0, c1, flags, n, max_dist, idx_out, d_out, count_out);
+    });
+}
+
+int gdist_ctx_cross_info(gdist_ctx* ctx, double* join_ms, double* select_ms, int64_t* units) {
+    return guard([&] {
+        GD_REQUIRE(ctx != nullptr, "null context");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        if (join_ms) *join_ms = ctx->cross_join_ms;
+        if (select_ms) *select_ms = ctx->cross_select_ms;
+        if (units) *units = ctx->cross_units;
     });
 }
 

@@ -353,6 +353,11 @@ struct gdist_ctx {
     // the distinct-row groups of its list and the work units launched for them
     double pairs_kernel_ms = -1.0;
     int64_t pairs_groups = 0, pairs_units = 0;
+    // the last gdist_cross_matrix / gdist_cross_closest call: its join kernel and its
+    // select (or epilogue) kernel, ms over all steps (-1 unless option time_kernels = 1),
+    // and the work units launched
+    double cross_join_ms = -1.0, cross_select_ms = -1.0;
+    int64_t cross_units = 0;
     gdist_ctx() { for (auto& o : opt) o = gdist::kOptUnset; }
     int64_t option(gdist::Opt o, int64_t dflt) const { return opt[o] == gdist::kOptUnset ? dflt : opt[o]; }
     bool has_option(gdist::Opt o) const { return opt[o] != gdist::kOptUnset; }
@@ -698,6 +703,9 @@ void sorted_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
                    int64_t c1, bool upper, int32_t* d_I, int64_t ldI);
 void sorted_row(gdist_ctx* ctx, const gdist_sets* s, int64_t q, const int64_t* d_cols, int64_t ncols,
                 int32_t* d_I);
+// segment index rows of any sets by any splitters: d_out[nsets][nseg + 1], positions into d_codes
+void segment_rows(gdist_ctx* ctx, const uint64_t* d_codes, const int64_t* d_off, int64_t nsets,
+                  const uint64_t* d_split, int nseg, int64_t* d_out);
 
 void bitset_row(gdist_ctx* ctx, const gdist_sets* s, int64_t q, const int64_t* d_cols, int64_t ncols,
                 int32_t* d_I);
@@ -719,6 +727,21 @@ void distance_epilogue(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t 
 void closest_blocks(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem, int64_t* rows, int64_t* cols);
 void closest(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
              unsigned flags, int n, double max_dist, int64_t* idx_out, double* d_out, int32_t* count_out);
+
+// one select step of closest() over counts whose rows and columns belong to
+// two collections (their offsets d_roff / d_coff); no column is left out as self
+void closest_select_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff,
+                           const int64_t* d_coff, int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc,
+                           int n, int L, double max_dist, unsigned long long* st_d, uint32_t* st_c, int32_t* st_n,
+                           int last, int64_t* d_idx, double* d_d, int32_t* d_count);
+
+// cross.hip — query sets against a resident collection (gdist_cross_matrix / gdist_cross_closest)
+// every argument checked by the caller, the subjects' segment index built; host outputs
+void cross_matrix(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
+                  int64_t c1, unsigned flags, int32_t* I_out, double* D_out, int64_t ld);
+void cross_closest(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
+                   int64_t c1, unsigned flags, int n, double max_dist, int64_t* idx_out, double* d_out,
+                   int32_t* count_out);
 
 // group.hip — in-group / out-group distance summary (gdist_group_stats)
 // method: SORTED or BITSET (resolved by the caller); ignored for sketches.

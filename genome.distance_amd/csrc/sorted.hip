@@ -239,6 +239,17 @@ void extend_segments(gdist_ctx* ctx, gdist_sets* s, int64_t n_old) {
     s->segoff = std::move(grown);
 }
 
+// Rows of a segment index for any sets cut by any splitters (cross.hip: query
+// sets by the subjects' splitters): out[s][t], nsets x (nseg + 1) positions
+// into `codes`; d_off holds nsets + 1 offsets
+void segment_rows(gdist_ctx* ctx, const uint64_t* d_codes, const int64_t* d_off, int64_t nsets,
+                  const uint64_t* d_split, int nseg, int64_t* d_out) {
+    const int64_t n = nsets * (int64_t)(nseg + 1);
+    if (n <= 0) return;
+    segoff_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, ctx->stream>>>(d_codes, d_off, nsets, d_split, nseg, d_out);
+    GD_HIP(hipGetLastError());
+}
+
 static void launch_join(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1,
                         const int64_t* d_colidx, bool upper, int32_t* d_I, int64_t ldI) {
     hipStream_t st = ctx->stream;

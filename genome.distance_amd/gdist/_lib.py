@@ -59,12 +59,13 @@ _REPO = os.path.dirname(_PKG)
 def tree_source_hash() -> str:
     """sha256 prefix of the library's sources in this tree, in the Makefile's
     order (csrc/*.hip by name, csrc/gdist_internal.hpp, csrc/sparse_bounds.hpp,
-    csrc/group_stats_host.hpp, include/gdist.h)."""
+    csrc/group_stats_host.hpp, csrc/cross_plan.hpp, include/gdist.h)."""
     import glob
     import hashlib
     files = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hip")))
     files += [os.path.join(_PKG, "csrc", "gdist_internal.hpp"), os.path.join(_PKG, "csrc", "sparse_bounds.hpp"),
-              os.path.join(_PKG, "csrc", "group_stats_host.hpp"), os.path.join(_REPO, "include", "gdist.h")]
+              os.path.join(_PKG, "csrc", "group_stats_host.hpp"), os.path.join(_PKG, "csrc", "cross_plan.hpp"),
+              os.path.join(_REPO, "include", "gdist.h")]
     h = hashlib.sha256()
     for f in files:
         with open(f, "rb") as fh:
@@ -156,6 +157,10 @@ _SIGS = {
     "gdist_ctx_within_timing": (C.c_int, [_ctxp, _dblp, _dblp]),
     "gdist_pairs": (C.c_int, [_ctxp, _setp, _i64, _i64p, _i64p, C.c_int, _u32, _i32p, _dblp]),
     "gdist_ctx_pairs_info": (C.c_int, [_ctxp, _dblp, _i64p, _i64p]),
+    "gdist_cross_matrix": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64, _i64, _i64, _u32, _i32p, _dblp, _i64]),
+    "gdist_cross_closest": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64, _i64, _i64, _u32, C.c_int, _dbl, _i64p, _dblp,
+                                      _i32p]),
+    "gdist_ctx_cross_info": (C.c_int, [_ctxp, _dblp, _dblp, _i64p]),
     "gdist_histogram": (C.c_int, [_ctxp, _setp, _i64, _i64, _i64, _i64, C.c_int, _u32, C.c_int, _dblp, C.c_int, _i32p,
                                   _i64p, _i64p, _i64p]),
     "gdist_ctx_histogram_timing": (C.c_int, [_ctxp, _dblp, _dblp]),

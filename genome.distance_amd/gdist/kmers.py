@@ -149,6 +149,16 @@ class Context:
         L.check(L.lib.gdist_ctx_histogram_timing(self.h, C.byref(m), C.byref(s)))
         return m.value, s.value
 
+    def cross_info(self) -> tuple[float, float, int]:
+        """(join kernel ms, select kernel ms, units) of the context's last
+        cross_matrix() / cross_closest() call (gdist_ctx_cross_info): the times
+        are summed over the steps and -1 unless option time_kernels = 1 (after
+        cross_matrix the second one is the distance epilogue); units are the
+        (query row, column block, segment range) work units launched."""
+        j, s, u = C.c_double(), C.c_double(), C.c_int64()
+        L.check(L.lib.gdist_ctx_cross_info(self.h, C.byref(j), C.byref(s), C.byref(u)))
+        return j.value, s.value, u.value
+
     def recent_timings(self, n: int) -> list[float]:
         """Kernel ms of the last n matrix calls, oldest first (waits for them)."""
         out = np.zeros(max(n, 1), dtype=np.float64)
@@ -621,6 +631,8 @@ class _Handle:
 class KmerSets(_Handle):
     """A collection of kmer sets (sorted unique uint64 codes) resident in HBM."""
 
+    pack_flags = 0   # the pack flags of from_sequences / from_blob / from_device (pack_like)
+
     @classmethod
     def from_sequences(cls, seqs: Sequence, k: int, kmer_type: KmerType = KmerType.DNA, flags: int = 0,
                        ctx: Context | None = None) -> "KmerSets":
@@ -633,7 +645,17 @@ class KmerSets(_Handle):
         h = C.c_void_p()
         L.check(L.lib.gdist_sets_pack(ctx.h, kmer_type.kind, int(k), flags, blob, L.ptr(off, C.c_int64),
                                       len(bs), C.byref(h)))
-        return cls(ctx, h)
+        sets = cls(ctx, h)
+        sets.pack_flags = flags
+        return sets
+
+    def pack_like(self, seqs: Sequence) -> "KmerSets":
+        """A new collection of `seqs` packed with this collection's kind, k and
+        pack flags (the flags it was packed with through this binding; 0 for a
+        collection of uploaded codes): queries for cross_matrix / cross_closest."""
+        kind, k, _, _ = self.info()
+        return KmerSets.from_sequences(seqs, k, KmerType.DNA if kind == L.DNA else KmerType.PROT, self.pack_flags,
+                                       self.ctx)
 
     def append(self, seqs: Sequence) -> int:
         """gdist_sets_append: pack `seqs` with this collection's kmer spec and
@@ -666,7 +688,9 @@ class KmerSets(_Handle):
         h = C.c_void_p()
         L.check(L.lib.gdist_sets_pack(ctx.h, kmer_type.kind, int(k), flags, ptr, L.ptr(off, C.c_int64), n,
                                       C.byref(h)))
-        return cls(ctx, h)
+        sets = cls(ctx, h)
+        sets.pack_flags = flags
+        return sets
 
     @classmethod
     def from_device(cls, ctx: Context, d_seqs: int, d_off: int, nseqs: int, total_bytes: int, k: int,
@@ -674,7 +698,9 @@ class KmerSets(_Handle):
         h = C.c_void_p()
         L.check(L.lib.gdist_sets_pack_device(ctx.h, kmer_type.kind, int(k), flags, d_seqs, d_off, nseqs,
                                              total_bytes, C.byref(h)))
-        return cls(ctx, h)
+        sets = cls(ctx, h)
+        sets.pack_flags = flags
+        return sets
 
     @classmethod
     def from_codes(cls, offsets: np.ndarray, codes: np.ndarray, k: int, kmer_type: KmerType = KmerType.DNA,
@@ -943,6 +969,48 @@ class KmerSets(_Handle):
         ms, g, u = C.c_double(), C.c_int64(), C.c_int64()
         L.check(L.lib.gdist_ctx_pairs_info(self.ctx.h, C.byref(ms), C.byref(g), C.byref(u)))
         return ms.value, g.value, u.value
+
+    def cross_matrix(self, queries: "KmerSets", rows: tuple[int, int] | None = None,
+                     cols: tuple[int, int] | None = None, flags: int = 0, want_I: bool = True,
+                     want_D: bool = True):
+        """|Q_i ∩ S_j| and distances of `queries` (rows) against this resident
+        collection (cols), host numpy outputs (gdist_cross_matrix). This
+        collection is only read (its segment index is built when absent) and
+        nothing is packed again: bit for bit the rectangle matrix(method=
+        METHOD_SORTED) gives for self.concat(queries). flags: EMPTY_NAN or 0."""
+        r0, r1 = rows or (0, len(queries))
+        c0, c1 = cols or (0, len(self))
+        nr, nc = max(r1 - r0, 0), max(c1 - c0, 0)
+        I = np.full((nr, nc), -1, dtype=np.int32) if want_I else None
+        D = np.full((nr, nc), np.nan, dtype=np.float64) if want_D else None
+        L.check(L.lib.gdist_cross_matrix(self.ctx.h, queries.h, self.h, r0, r1, c0, c1, flags,
+                                         L.ptr(I, C.c_int32) if want_I else None,
+                                         L.ptr(D, C.c_double) if want_D else None, max(nc, 1)))
+        return I, D
+
+    def cross_closest(self, queries: "KmerSets", n: int, max_dist: float, rows: tuple[int, int] | None = None,
+                      cols: tuple[int, int] | None = None, flags: int = 0):
+        """Exact nearest neighbours of `queries` among this resident collection
+        (gdist_cross_closest): for every query of `rows` the n sets of `cols`
+        with the smallest Jaccard distance <= max_dist, ordered by (distance,
+        index); no set is left out as the query itself. Returns (idx[nr, n]
+        int64, d[nr, n] float64, count[nr] int32) laid out as closest() lays
+        them out; d is cross_matrix()'s D bit for bit. This collection is only
+        read and nothing is packed again."""
+        r0, r1 = rows or (0, len(queries))
+        c0, c1 = cols or (0, len(self))
+        nr = max(r1 - r0, 0)
+        idx = np.full((nr, max(n, 0)), -1, dtype=np.int64)
+        d = np.ones((nr, max(n, 0)), dtype=np.float64)
+        cnt = np.zeros(nr, dtype=np.int32)
+        # non-empty buffers behind empty results: the library is never handed a null output
+        bi = idx if idx.size else np.zeros(1, dtype=np.int64)
+        bd = d if d.size else np.zeros(1, dtype=np.float64)
+        bc = cnt if cnt.size else np.zeros(1, dtype=np.int32)
+        L.check(L.lib.gdist_cross_closest(self.ctx.h, queries.h, self.h, r0, r1, c0, c1, flags, int(n),
+                                          float(max_dist), L.ptr(bi, C.c_int64), L.ptr(bd, C.c_double),
+                                          L.ptr(bc, C.c_int32)))
+        return idx, d, cnt
 
     def row_query(self, q: int, cols: Iterable[int], mode: int = L.QUERY_ALL, t: float = 1.0):
         cl = np.ascontiguousarray(np.fromiter(cols, dtype=np.int64))

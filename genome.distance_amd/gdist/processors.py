@@ -405,6 +405,57 @@ def closest_genomes(queries: Sequence[Genome], subjects: Sequence[Genome], out: 
     return nq, found, none
 
 
+def find_genomes(db: KmerSets, subjects: Sequence[Genome], queries: Iterable[Genome], out: TextIO,
+                 neighbors: int = 10, max_dist: float = 0.9, batch: int = 64) -> tuple[int, int]:
+    """The `find` table over a resident database: `db` holds the kmer sets of
+    `subjects` (set j is subjects[j]) and stays on the device as it is, as the
+    reference loads its genome database once and then answers one getClosest
+    per incoming genome. The queries are packed `batch` at a time with the
+    database's k and pack flags and go through KmerSets.cross_closest; the
+    database is never packed again. Neighbours are exact (every subject, not
+    the LSH buckets), nearest first, ties by subject order. The neighbour's id
+    and name are one field with a tab inside, as the database returns them.
+    Returns (neighbours found, searches with none), the counters of the
+    reference's closing log line."""
+    # the database loaded once, one getClosest per genome: FindProcessor.java:94-110
+    # defaults (10 neighbours, 0.9): FindProcessor.java:72-73
+    # the header: FindProcessor.java:100
+    out.write("genome_id\tgenome_name\tneighbor_id\tneighbor_name\tdistance\n")
+    if len(db) != len(subjects):
+        raise ValueError(f"the database holds {len(db)} sets but {len(subjects)} subjects were named")
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    found = fail = 0
+
+    def flush(group):
+        nonlocal found, fail
+        qs = db.pack_like([g.kmer_text() for g in group])
+        try:
+            idx, d, cnt = db.cross_closest(qs, neighbors, max_dist)
+        finally:
+            qs.free()
+        for a, q in enumerate(group):
+            # no neighbour counts as a failure: FindProcessor.java:111
+            if cnt[a] == 0:
+                fail += 1
+            for r in range(cnt[a]):
+                s = subjects[int(idx[a, r])]
+                # the row format "%s\t%s\t%s\t%8.3f%n": FindProcessor.java:113-114
+                out.write(f"{q.id}\t{q.name}\t{s.id}\t{s.name}\t{java_format_f(float(d[a, r]), 8, 3)}\n")
+                found += 1
+
+    group = []
+    for g in queries:
+        group.append(g)
+        if len(group) >= batch:
+            flush(group)
+            group = []
+    if group:
+        flush(group)
+    # the counters of the closing log line: FindProcessor.java:119
+    return found, fail
+
+
 def group_labels(ids: Sequence[str], groupings: dict) -> tuple[list[str], np.ndarray]:
     """(type names, int32 labels [T, N]) of `groupings` (type name -> {genome id
     -> group id}) for the sets `ids`: group ids become integers by first

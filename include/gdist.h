@@ -31,6 +31,10 @@
  *                          (every pair with d <= maxDist)
  *   gdist_pairs            getDistance over an (id1, id2) list   MethodTableProcessor.java:258-276
  *                          the lists of the pairs commands       BasicPairsProcessor.java:71-89, PairCreateProcessor.java:29-32
+ *   gdist_cross_closest    getClosest(kmers, n, maxDist) per new genome
+ *                          against the loaded genome database    FindProcessor.java:94-110, MashProcessor.java:150
+ *   gdist_cross_matrix     the same queries x database rectangle
+ *                          as counts and distances               GenomeProcessor.java:140
  *   gdist_group_stats      recordDistance over a distance table  GroupTypeSpec.java:77-95
  *                          in / out-group min, mean, sd, max     DistanceCheckProcessor.java:200-223
  *   gdist_histogram        new Distributor(0.0, 1.0, 50)         TaxCheckProcessor.java:93
@@ -545,6 +549,68 @@ int  gdist_pairs(gdist_ctx* ctx, const gdist_sets* sets, int64_t npairs,
 /* last gdist_pairs call: kernel time (ms; -1 unless option "time_kernels" = 1), the
  * distinct-row groups of the list and the work units launched for them */
 int  gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, int64_t* units);
+
+/* ---- new query sets against a resident collection ---------------------- */
+/* The reference loads its genome database once and answers one
+ * getClosest(kmers, n, maxDist) per incoming genome (FindProcessor.java:94-110,
+ * MashProcessor.java:150). `subjects` is that database: a kmer-set collection
+ * that stays as it is. `queries` is another collection of the same context and
+ * kmer spec (what gdist_sets_concat would accept; GDIST_NO_CASE_FOLD may
+ * differ). Rows are query sets [q0, q1), columns subject sets [c0, c1).
+ *
+ * gdist_cross_matrix: I_out[(i-q0)*ld + (j-c0)] = |Q_i ∩ S_j| and D_out
+ * likewise the distance (host arrays, either may be NULL), the header's Java
+ * expression with |A| from the queries' sizes and |B| from the subjects';
+ * GDIST_EMPTY_NAN is honoured. Bit for bit what
+ * gdist_intersect_matrix(GDIST_METHOD_SORTED) writes for rows
+ * [ns+q0, ns+q1) x cols [c0, c1) of gdist_sets_concat(subjects, queries),
+ * ns = the subjects' sets. Cells outside the rectangle, the ld padding
+ * included, are not touched. The rectangle is walked in row blocks x column
+ * chunks sized like gdist_closest's (device scratch is bounded).
+ *
+ * gdist_cross_closest: for every query row the subjects j in [c0, c1) with
+ * d <= max_dist, ordered by (d as fp64, j), the first n. Output layout, fill
+ * values (-1 / 1.0) and the NaN / d == 1.0 rules are gdist_closest's. No
+ * column is left out as "self": the collections are different, and the same
+ * handle passed for both behaves as GDIST_CLOSEST_KEEP_SELF. The counts stay
+ * on the device and D is never written; the walk takes the options
+ * "closest_rows" / "closest_cols".
+ *
+ * Both run the sorted join over work units (query row, <= 64 consecutive
+ * subject columns, a range of the subjects' segment index), so one query
+ * against many subjects still fills the device; kmer sets only (the pruned
+ * dictionary of the subjects cannot answer for kmers that only a query and
+ * one subject share; sketches: gdist_lsh_closest).
+ *
+ * The subjects are read only: bitsets, tiers, launch plans, captured graphs,
+ * codes and the number of sets are as before the call. The one thing a cross
+ * call adds, when absent, is the subjects' segment index of the sorted join,
+ * exactly as a GDIST_METHOD_SORTED call on them does; like after such a call,
+ * a later GDIST_METHOD_AUTO on subjects without bitsets stays on the sorted
+ * join instead of trying the dictionary build. Nothing is kept on the queries.
+ *
+ * An empty row or column range: GDIST_OK; the matrix outputs are untouched,
+ * the closest counts are 0 with slots -1 / 1.0 (n == 0 likewise). EINVAL,
+ * decided before any work with every output untouched: a null handle,
+ * collections of another context or of different contexts, a GDIST_SKETCH
+ * collection, kmer specs gdist_sets_concat would refuse, a collection without
+ * codes (released, or from gdist_sets_allgather_bitsets), a range outside its
+ * collection, ld < c1 - c0, both matrix outputs NULL on a non-empty
+ * rectangle, any flag but GDIST_EMPTY_NAN, n < 0 or n > GDIST_CLOSEST_MAX_N,
+ * NaN max_dist, NULL closest outputs with a non-empty row range, subjects of
+ * 2^32 - 1 sets or more. */
+int  gdist_cross_matrix(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects,
+                        int64_t q0, int64_t q1, int64_t c0, int64_t c1, unsigned flags,
+                        int32_t* I_out, double* D_out, int64_t ld);
+int  gdist_cross_closest(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects,
+                         int64_t q0, int64_t q1, int64_t c0, int64_t c1, unsigned flags,
+                         int n, double max_dist,
+                         int64_t* idx_out, double* d_out, int32_t* count_out);
+/* last cross call: HIP-event time (ms, summed over the steps; -1 unless option
+ * "time_kernels" = 1) of the join kernel and of the kernel that follows it
+ * (gdist_cross_closest: the select; gdist_cross_matrix: the distance
+ * epilogue, 0 without D_out), and the work units launched */
+int  gdist_ctx_cross_info(gdist_ctx* ctx, double* join_ms, double* select_ms, int64_t* units);
 
 /* ---- distribution of the distances ------------------------------------- */
 /* How the distances of a rectangle are distributed over caller-supplied
