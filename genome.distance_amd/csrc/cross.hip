@@ -25,6 +25,14 @@
 // per-column counts stay in LDS; at the unit's end the non-zero ones are added
 // to the zeroed I block with atomicAdd: integers, so the sum over a (row,
 // block)'s units is exact and order-free.
+//
+// Consumers. A step's counts never leave the device; what follows the join
+// differs by entry point: the distance epilogue (gdist_cross_matrix), the
+// top-n select (gdist_cross_closest), the CSR compaction of within.hip
+// (gdist_cross_within), the limb sums of group.hip (gdist_cross_group_stats)
+// and the bucket counts of hist.hip (gdist_cross_histogram). Each is the
+// kernel its one-collection twin runs, given the queries' offsets and labels
+// for the rows and the subjects' for the columns.
 #include <algorithm>
 #include <cstring>
 
@@ -163,7 +171,7 @@ __global__ __launch_bounds__(256) void cross_epilogue_kernel(const int64_t* __re
     }
 }
 
-// The walk both entry points share: row blocks x ascending column chunks. Per
+// The walk every entry point shares: row blocks x ascending column chunks. Per
 // row block the queries' segment rows; per step the plan, the zeroed counts
 // and the join. `after(b0, nb, k0, nk, last)` queues the kernels that consume
 // the step's counts (blk: [nb][nk] int32, inside the timed span), then
@@ -232,6 +240,22 @@ struct CrossWalk {
                 out(b0, nb, k0, nk, k1 == c1 ? 1 : 0);
                 nunits += nu;
             }
+        }
+    }
+
+    // a consumer kernel that can only be queued from `out` (it needs what the
+    // step downloaded): its time joins select_ms
+    template <class F>
+    void timed_select(F&& f) {
+        hipStream_t st = ctx->stream;
+        if (timed) GD_HIP(hipEventRecord(ev[1], st));
+        f();
+        if (timed) {
+            GD_HIP(hipEventRecord(ev[2], st));
+            GD_HIP(hipEventSynchronize(ev[2]));
+            float sl = 0;
+            GD_HIP(hipEventElapsedTime(&sl, ev[1], ev[2]));
+            select_ms += sl;
         }
     }
 
@@ -314,6 +338,106 @@ void cross_closest(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int
         }
     });
     walk.report();
+}
+
+// as cross_matrix; a non-empty rectangle. A row needs its full column width
+// before it can be compacted in (row, column) order: the walk is by row blocks
+// of within()'s sizing over all of [c0, c1), one step a block, and the steps
+// arrive in row order
+void cross_within(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
+                  int64_t c1, unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr, int64_t* col_out,
+                  double* d_out) {
+    hipStream_t st = ctx->stream;
+    const int empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
+    const int64_t nc = c1 - c0;
+    const int64_t R = within_rows(ctx, q1 - q0, nc, 4);
+    CrossWalk walk(ctx, q, s, R, nc);
+    const int64_t max_tiles = within_tiles(R, nc);
+    DevBuf tcount((size_t)(max_tiles + 1) * 4, st), tbase((size_t)(max_tiles + 1) * 8, st);
+    DevBuf rbase((size_t)(R + 1) * 8, st), scan_tmp;
+    std::vector<int64_t> hbase((size_t)R + 1);
+    int64_t total = 0;   // pairs of the rows before this step
+    rowptr[0] = 0;
+    walk.run(q0, q1, c0, c1, [&](int64_t b0, int64_t nb, int64_t k0, int64_t nk, int) {
+        within_count_counts(ctx, walk.blk.as<int32_t>(), nk, q->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan, b0,
+                            nb, k0, nk, max_dist, tcount.as<int32_t>(), tbase.as<int64_t>(), rbase.as<int64_t>(),
+                            scan_tmp);
+    }, [&](int64_t b0, int64_t nb, int64_t k0, int64_t nk, int) {
+        d2h(hbase.data(), rbase.p, (size_t)(nb + 1) * 8, st);
+        int64_t* rp = rowptr + (b0 - q0);
+        for (int64_t a = 0; a <= nb; a++) rp[a] = total + hbase[a];
+        const int64_t step = hbase[nb];
+        const int64_t fit = std::min(step, std::max<int64_t>(capacity - total, 0));
+        if (fit > 0) {
+            DevBuf sc((size_t)fit * 8, st), sd((size_t)fit * 8, st);
+            walk.timed_select([&] {
+                within_write_counts(ctx, walk.blk.as<int32_t>(), nk, q->off.as<int64_t>(), s->off.as<int64_t>(),
+                                    empty_nan, b0, nb, k0, nk, max_dist, tbase.as<int64_t>(), fit, sc.as<int64_t>(),
+                                    sd.as<double>());
+            });
+            d2h(col_out + total, sc.p, (size_t)fit * 8, st);
+            d2h(d_out + total, sd.p, (size_t)fit * 8, st);
+        }
+        total += step;
+    });
+    walk.report();
+}
+
+// as cross_matrix, any rectangle (an empty one: the n == 0 form). Each step's
+// counts are folded into the call's accumulators, as group_stats() folds them
+void cross_group_stats(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
+                       int64_t c1, unsigned flags, int ntypes, const int32_t* qlabels, const int32_t* slabels,
+                       gdist_group_side* out, int64_t* bad) {
+    hipStream_t st = ctx->stream;
+    const int empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
+    const size_t nslots = group_slots(ntypes);
+    std::vector<unsigned long long> h(nslots, 0ull);
+    if (q1 > q0 && c1 > c0) {
+        int64_t R, W;
+        closest_blocks(ctx, q1 - q0, c1 - c0, 4, &R, &W);
+        CrossWalk walk(ctx, q, s, R, W);
+        DevBuf qlab((size_t)ntypes * q->nsets * 4, st), slab((size_t)ntypes * s->nsets * 4, st), acc(nslots * 8, st);
+        h2d(qlab.p, qlabels, (size_t)ntypes * q->nsets * 4, st);
+        h2d(slab.p, slabels, (size_t)ntypes * s->nsets * 4, st);
+        GD_HIP(hipMemsetAsync(acc.p, 0, nslots * 8, st));
+        walk.run(q0, q1, c0, c1, [&](int64_t b0, int64_t nb, int64_t k0, int64_t nk, int) {
+            group_reduce_counts(ctx, walk.blk.as<int32_t>(), nk, q->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan,
+                                b0, nb, k0, nk, ntypes, qlab.as<int32_t>(), q->nsets, slab.as<int32_t>(), s->nsets,
+                                acc.as<unsigned long long>());
+        }, [](int64_t, int64_t, int64_t, int64_t, int) {});
+        d2h(h.data(), acc.p, nslots * 8, st);
+        walk.report();
+    }
+    group_finish(h.data(), ntypes, out, bad);
+}
+
+// as cross_group_stats with the bucket counts of histogram()
+void cross_histogram(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
+                     int64_t c1, unsigned flags, int nedges, const double* edges, int ntypes, const int32_t* qlabels,
+                     const int32_t* slabels, int64_t* counts, int64_t* nans, int64_t* bad) {
+    hipStream_t st = ctx->stream;
+    const int empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
+    const size_t nslots = hist_slots(nedges, ntypes);
+    std::vector<unsigned long long> h(nslots, 0ull);
+    if (q1 > q0 && c1 > c0) {
+        int64_t R, W;
+        closest_blocks(ctx, q1 - q0, c1 - c0, 4, &R, &W);
+        CrossWalk walk(ctx, q, s, R, W);
+        DevBuf qlab((size_t)ntypes * q->nsets * 4, st), slab((size_t)ntypes * s->nsets * 4, st);
+        DevBuf edg((size_t)nedges * 8, st), acc(nslots * 8, st);
+        h2d(qlab.p, qlabels, (size_t)ntypes * q->nsets * 4, st);
+        h2d(slab.p, slabels, (size_t)ntypes * s->nsets * 4, st);
+        h2d(edg.p, edges, (size_t)nedges * 8, st);
+        GD_HIP(hipMemsetAsync(acc.p, 0, nslots * 8, st));
+        walk.run(q0, q1, c0, c1, [&](int64_t b0, int64_t nb, int64_t k0, int64_t nk, int) {
+            hist_counts(ctx, walk.blk.as<int32_t>(), nk, q->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan, b0, nb,
+                        k0, nk, ntypes, qlab.as<int32_t>(), q->nsets, slab.as<int32_t>(), s->nsets, edg.as<double>(),
+                        nedges, acc.as<unsigned long long>());
+        }, [](int64_t, int64_t, int64_t, int64_t, int) {});
+        d2h(h.data(), acc.p, nslots * 8, st);
+        walk.report();
+    }
+    hist_finish(h.data(), nedges, ntypes, counts, nans, bad);
 }
 
 }  // namespace gdist

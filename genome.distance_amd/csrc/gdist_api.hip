@@ -1597,7 +1597,7 @@ int gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, int
 }
 
 // ---------------------------------------------------------------------------
-// what gdist_cross_matrix and gdist_cross_closest refuse alike, before any work
+// what every gdist_cross_* call refuses alike, before any work
 static void check_cross(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects, int64_t q0, int64_t q1,
                         int64_t c0, int64_t c1, unsigned flags) {
     check_sets(queries);
@@ -1663,6 +1663,83 @@ int gdist_cross_closest(gdist_ctx* ctx, const gdist_sets* queries, const gdist_s
         }
         if (!s->segoff.p) build_segments(ctx, s);
         gdist::cross_closest(ctx, queries, s, q0, q1, c0, c1, flags, n, max_dist, idx_out, d_out, count_out);
+    });
+}
+
+int gdist_cross_within(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects, int64_t q0, int64_t q1,
+                       int64_t c0, int64_t c1, unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr_out,
+                       int64_t* col_out, double* d_out, int64_t* total) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_cross(ctx, queries, subjects, q0, q1, c0, c1, flags);
+        GD_REQUIRE(max_dist == max_dist, "max_dist is NaN");
+        GD_REQUIRE(capacity >= 0, "negative capacity");
+        GD_REQUIRE(rowptr_out && total, "null rowptr_out or total");
+        GD_REQUIRE(capacity == 0 || (col_out && d_out), "null col_out or d_out with capacity > 0");
+        const int64_t nr = q1 - q0, nc = c1 - c0;
+        auto* s = const_cast<gdist_sets*>(subjects);
+        begin_cross(ctx);
+        // the row pointers into a local first: a failure on the device leaves them and *total untouched
+        std::vector<int64_t> rp((size_t)nr + 1, 0);
+        if (nr > 0 && nc > 0) {
+            if (!s->segoff.p) build_segments(ctx, s);
+            gdist::cross_within(ctx, queries, s, q0, q1, c0, c1, flags, max_dist, capacity, rp.data(), col_out, d_out);
+        }
+        std::copy(rp.begin(), rp.end(), rowptr_out);
+        *total = rp[(size_t)nr];
+    });
+}
+
+int gdist_cross_group_stats(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects, int64_t q0,
+                            int64_t q1, int64_t c0, int64_t c1, unsigned flags, int ntypes, const int32_t* qlabels,
+                            const int32_t* slabels, gdist_group_side* out, int64_t* bad) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_cross(ctx, queries, subjects, q0, q1, c0, c1, flags);
+        GD_REQUIRE(ntypes >= 1 && ntypes <= GDIST_GROUP_MAX_TYPES, "ntypes outside 1 .. GDIST_GROUP_MAX_TYPES");
+        GD_REQUIRE(qlabels && slabels && out && bad, "null labels or output");
+        auto* s = const_cast<gdist_sets*>(subjects);
+        begin_cross(ctx);
+        if (q1 > q0 && c1 > c0 && !s->segoff.p) build_segments(ctx, s);
+        // into locals first: a failure on the device leaves the outputs untouched too
+        std::vector<gdist_group_side> o((size_t)2 * ntypes);
+        std::vector<int64_t> b((size_t)ntypes);
+        gdist::cross_group_stats(ctx, queries, s, q0, q1, c0, c1, flags, ntypes, qlabels, slabels, o.data(), b.data());
+        std::copy(o.begin(), o.end(), out);
+        std::copy(b.begin(), b.end(), bad);
+    });
+}
+
+int gdist_cross_histogram(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects, int64_t q0, int64_t q1,
+                          int64_t c0, int64_t c1, unsigned flags, int nedges, const double* edges, int ntypes,
+                          const int32_t* qlabels, const int32_t* slabels, int64_t* counts_out, int64_t* nans_out,
+                          int64_t* bad_out) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_cross(ctx, queries, subjects, q0, q1, c0, c1, flags);
+        GD_REQUIRE(nedges >= 1 && nedges <= GDIST_HIST_MAX_EDGES, "nedges outside 1 .. GDIST_HIST_MAX_EDGES");
+        GD_REQUIRE(ntypes >= 0 && ntypes <= GDIST_GROUP_MAX_TYPES, "ntypes outside 0 .. GDIST_GROUP_MAX_TYPES");
+        GD_REQUIRE(edges && counts_out && nans_out, "null edges or output");
+        GD_REQUIRE(ntypes == 0 || (qlabels && slabels && bad_out), "null labels or bad_out with ntypes > 0");
+        for (int e = 0; e < nedges; e++) {
+            GD_REQUIRE(edges[e] == edges[e], "an edge is NaN");
+            // -0.0 == 0.0: a signed-zero pair is not ascending either
+            GD_REQUIRE(e == 0 || edges[e - 1] < edges[e], "edges are not strictly ascending");
+        }
+        auto* s = const_cast<gdist_sets*>(subjects);
+        begin_cross(ctx);
+        if (q1 > q0 && c1 > c0 && !s->segoff.p) build_segments(ctx, s);
+        // into locals first: a failure on the device leaves the outputs untouched too
+        const size_t series = ntypes ? (size_t)2 * ntypes : 1;
+        std::vector<int64_t> cn(series * ((size_t)nedges + 1)), na(series), b((size_t)ntypes);
+        gdist::cross_histogram(ctx, queries, s, q0, q1, c0, c1, flags, nedges, edges, ntypes, qlabels, slabels,
+                               cn.data(), na.data(), b.data());
+        std::copy(cn.begin(), cn.end(), counts_out);
+        std::copy(na.begin(), na.end(), nans_out);
+        if (ntypes) std::copy(b.begin(), b.end(), bad_out);
     });
 }
 

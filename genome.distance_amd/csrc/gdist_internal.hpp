@@ -353,8 +353,8 @@ struct gdist_ctx {
     // the distinct-row groups of its list and the work units launched for them
     double pairs_kernel_ms = -1.0;
     int64_t pairs_groups = 0, pairs_units = 0;
-    // the last gdist_cross_matrix / gdist_cross_closest call: its join kernel and its
-    // select (or epilogue) kernel, ms over all steps (-1 unless option time_kernels = 1),
+    // the last gdist_cross_* call: its join kernel and its consumer (select, epilogue,
+    // compaction, reduce or histogram) kernels, ms over all steps (-1 unless option time_kernels = 1),
     // and the work units launched
     double cross_join_ms = -1.0, cross_select_ms = -1.0;
     int64_t cross_units = 0;
@@ -735,19 +735,40 @@ void closest_select_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const
                            int n, int L, double max_dist, unsigned long long* st_d, uint32_t* st_c, int32_t* st_n,
                            int last, int64_t* d_idx, double* d_d, int32_t* d_count);
 
-// cross.hip — query sets against a resident collection (gdist_cross_matrix / gdist_cross_closest)
+// cross.hip — query sets against a resident collection (gdist_cross_*)
 // every argument checked by the caller, the subjects' segment index built; host outputs
 void cross_matrix(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
                   int64_t c1, unsigned flags, int32_t* I_out, double* D_out, int64_t ld);
 void cross_closest(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
                    int64_t c1, unsigned flags, int n, double max_dist, int64_t* idx_out, double* d_out,
                    int32_t* count_out);
+// the same walk with the other consumers of the counts; rowptr: q1 - q0 + 1
+// entries, written whole (an empty rectangle is the caller's)
+void cross_within(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
+                  int64_t c1, unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr, int64_t* col_out,
+                  double* d_out);
+void cross_group_stats(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
+                       int64_t c1, unsigned flags, int ntypes, const int32_t* qlabels, const int32_t* slabels,
+                       gdist_group_side* out, int64_t* bad);
+void cross_histogram(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
+                     int64_t c1, unsigned flags, int nedges, const double* edges, int ntypes, const int32_t* qlabels,
+                     const int32_t* slabels, int64_t* counts, int64_t* nans, int64_t* bad);
 
 // group.hip — in-group / out-group distance summary (gdist_group_stats)
 // method: SORTED or BITSET (resolved by the caller); ignored for sketches.
 // labels: host, [ntypes][nsets]; out: [ntypes][2], bad: [ntypes], written whole
 void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
                  unsigned flags, int ntypes, const int32_t* labels, gdist_group_side* out, int64_t* bad);
+// one reduce step of group_stats() over counts whose rows and columns belong
+// to two collections (offsets d_roff / d_coff, labels d_rlab [ntypes][nrsets] /
+// d_clab [ntypes][ncsets]); every cell counts. d_acc: group_slots(ntypes)
+// uint64, zeroed by the caller; group_finish turns its host copy into the sides
+size_t group_slots(int ntypes);
+void group_reduce_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
+                         int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, int ntypes,
+                         const int32_t* d_rlab, int64_t nrsets, const int32_t* d_clab, int64_t ncsets,
+                         unsigned long long* d_acc);
+void group_finish(const unsigned long long* h, int ntypes, gdist_group_side* out, int64_t* bad);
 
 // within.hip — every pair within max_dist as CSR (gdist_within)
 // method: SORTED or BITSET (resolved by the caller); ignored for sketches.
@@ -756,6 +777,18 @@ void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t 
 int64_t within_rows(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem);
 void within(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
             unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr, int64_t* col_out, double* d_out);
+// the compaction of within() over one row block's counts whose rows and
+// columns belong to two collections; every cell may qualify. count: the tile
+// counts (d_tcount: within_tiles + 1 int32), their scan (d_tbase: as many
+// int64) and the rows' bases (d_rbase: nrows + 1). write: the survivors at
+// positions < fit into d_col / d_d
+int64_t within_tiles(int64_t nrows, int64_t nc);
+void within_count_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
+                         int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, double max_dist,
+                         int32_t* d_tcount, int64_t* d_tbase, int64_t* d_rbase, DevBuf& scan_tmp);
+void within_write_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
+                         int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, double max_dist,
+                         const int64_t* d_tbase, int64_t fit, int64_t* d_col, double* d_d);
 
 // hist.hip — distribution of the distances over bucket edges (gdist_histogram)
 // method: SORTED or BITSET (resolved by the caller, every argument checked);
@@ -765,6 +798,15 @@ void within(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, i
 void histogram(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
                unsigned flags, int nedges, const double* edges, int ntypes, const int32_t* labels, int64_t* counts,
                int64_t* nans, int64_t* bad);
+// one counting step of histogram() over counts whose rows and columns belong
+// to two collections (as group_reduce_counts; the labels are not read when
+// ntypes == 0). d_acc: hist_slots(nedges, ntypes) uint64, zeroed by the caller
+size_t hist_slots(int nedges, int ntypes);
+void hist_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
+                 int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, int ntypes,
+                 const int32_t* d_rlab, int64_t nrsets, const int32_t* d_clab, int64_t ncsets, const double* d_edges,
+                 int nedges, unsigned long long* d_acc);
+void hist_finish(const unsigned long long* h, int nedges, int ntypes, int64_t* counts, int64_t* nans, int64_t* bad);
 
 // pairs.hip — the distances of a pair list (gdist_pairs)
 // method: SORTED or BITSET (resolved by the caller, every argument checked);

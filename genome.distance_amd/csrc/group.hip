@@ -71,16 +71,21 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
 //  FromCounts: src is I (int32, row a / column b at src[a * ld + b]) and d is
 //  the Java expression of epilogue_kernel (bitset.hip) and
 //  closest_select_kernel, fp64, no contraction; else src is D (double).
+//  The row's size and label come from roff / rlabels ([.][nrsets]), the
+//  column's from coff / clabels ([.][ncsets]): one collection passes the same
+//  pointers twice, the cross calls (cross.hip) the queries' and the subjects'.
 template <bool FromCounts>
 __global__ __launch_bounds__(256) void group_reduce_kernel(
-    const void* __restrict__ src, int64_t ld, const int64_t* __restrict__ off, int empty_nan, int64_t q0,
-    int64_t nrows, int64_t c0, int64_t nc, int upper, const int32_t* __restrict__ labels, int64_t nsets,
+    const void* __restrict__ src, int64_t ld, const int64_t* __restrict__ roff, const int64_t* __restrict__ coff,
+    int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, int upper,
+    const int32_t* __restrict__ rlabels, int64_t nrsets, const int32_t* __restrict__ clabels, int64_t ncsets,
     int64_t nitems, int64_t nseg, unsigned long long* __restrict__ acc) {
 #pragma clang fp contract(off)
     __shared__ unsigned long long red[4][kTypeSlots];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int type = blockIdx.y;
-    const int32_t* lab = labels + (int64_t)type * nsets;
+    const int32_t* rlab = rlabels + (int64_t)type * nrsets;
+    const int32_t* clab = clabels + (int64_t)type * ncsets;
     const int64_t nwaves = (int64_t)gridDim.x * 4;
 
     LaneSide sd[2];
@@ -95,15 +100,15 @@ __global__ __launch_bounds__(256) void group_reduce_kernel(
         const int64_t bend = min(nc, b0 + (int64_t)kSegCols);
         const int64_t q = q0 + a;
         if (upper && c0 + bend - 1 <= q) continue;   // wholly on or left of the diagonal (wave-uniform)
-        const int32_t la = lab[q];
+        const int32_t la = rlab[q];
         int64_t na = 0;
-        if (FromCounts) na = off[q + 1] - off[q];
+        if (FromCounts) na = roff[q + 1] - roff[q];
         const int32_t* Ir = static_cast<const int32_t*>(src) + a * ld;
         const double* Dr = static_cast<const double*>(src) + a * ld;
         for (int64_t b = b0 + lane; b < bend; b += 64) {
             const int64_t j = c0 + b;
             if (upper && j <= q) continue;
-            const int32_t lb = lab[j];
+            const int32_t lb = clab[j];
             if ((la | lb) < 0) {
                 bad++;
                 continue;
@@ -111,7 +116,7 @@ __global__ __launch_bounds__(256) void group_reduce_kernel(
             double d;
             if (FromCounts) {
                 const int64_t inter = Ir[b];
-                const int64_t nb = off[j + 1] - off[j];
+                const int64_t nb = coff[j + 1] - coff[j];
                 if (inter > 0) {
                     const double uni = (double)(na + nb - inter);
                     d = 1.0 - (double)inter / uni;
@@ -215,7 +220,58 @@ __global__ __launch_bounds__(256) void group_reduce_kernel(
     }
 }
 
+// enough waves for ~4 a SIMD, and never more than kMaxItemsPerWave items a
+// wave (the kernel's overflow bound)
+dim3 group_grid(const gdist_ctx* ctx, int64_t nrows, int64_t nc, int ntypes) {
+    const int64_t nitems = nrows * ceil_div(nc, kSegCols);
+    const int64_t waves =
+        std::max(std::min<int64_t>(nitems, (int64_t)ctx->cus * 16), ceil_div(nitems, kMaxItemsPerWave));
+    return dim3((unsigned)ceil_div(waves, 4), (unsigned)ntypes);
+}
+
 }  // namespace
+
+size_t group_slots(int ntypes) { return (size_t)ntypes * kTypeSlots; }
+
+void group_reduce_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
+                         int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, int ntypes,
+                         const int32_t* d_rlab, int64_t nrsets, const int32_t* d_clab, int64_t ncsets,
+                         unsigned long long* d_acc) {
+    const dim3 grid = group_grid(ctx, nrows, nc, ntypes);
+    const int64_t nseg = ceil_div(nc, kSegCols);
+    group_reduce_kernel<true><<<grid, 256, 0, ctx->stream>>>(d_I, ld, d_roff, d_coff, empty_nan, q0, nrows, c0, nc, 0,
+                                                             d_rlab, nrsets, d_clab, ncsets, nrows * nseg, nseg,
+                                                             d_acc);
+    GD_HIP(hipGetLastError());
+}
+
+// carries of the digit slots, min / max from their patterns, mean and sdev
+void group_finish(const unsigned long long* h, int ntypes, gdist_group_side* out, int64_t* bad) {
+    for (int t = 0; t < ntypes; t++) {
+        const unsigned long long* g = h + (size_t)t * kTypeSlots;
+        for (int k = 0; k < 2; k++) {
+            const unsigned long long* w = g + k * kSideSlots;
+            gdist_group_side o;
+            std::memset(&o, 0, sizeof(o));
+            o.n = (int64_t)w[0];
+            o.ones = (int64_t)w[1];
+            o.nans = (int64_t)w[2];
+            gstats::U256 S, Q;
+            for (int d = 0; d < 4; d++) gstats::add_digit(S, w[3 + d], d);
+            for (int d = 0; d < 6; d++) gstats::add_digit(Q, w[7 + d], d);
+            if (S.w[2] | S.w[3] | Q.w[3]) throw Error(GDIST_EDEVICE, "group statistics: a sum exceeds its limbs");
+            o.sum[0] = S.w[0];
+            o.sum[1] = S.w[1];
+            for (int i = 0; i < 3; i++) o.sumsq[i] = Q.w[i];
+            const unsigned long long mn = ~w[13], mx = w[14];
+            std::memcpy(&o.min, &mn, 8);
+            std::memcpy(&o.max, &mx, 8);
+            gstats::finish(&o);
+            out[2 * t + k] = o;
+        }
+        bad[t] = (int64_t)g[2 * kSideSlots];
+    }
+}
 
 void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
                  unsigned flags, int ntypes, const int32_t* labels, gdist_group_side* out, int64_t* bad) {
@@ -260,20 +316,17 @@ void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t 
                     sorted_matrix(ctx, s, b0, b1, k0, k1, false, blk.as<int32_t>(), nk);
                 }
                 if (timed) GD_HIP(hipEventRecord(ev[1], st));
-                // enough waves for ~4 a SIMD, and never more than
-                // kMaxItemsPerWave items a wave (the kernel's overflow bound)
+                const dim3 grid = group_grid(ctx, nb, nk, ntypes);
                 const int64_t nseg = ceil_div(nk, kSegCols), nitems = nb * nseg;
-                const int64_t waves = std::max(std::min<int64_t>(nitems, (int64_t)ctx->cus * 16),
-                                               ceil_div(nitems, kMaxItemsPerWave));
-                const dim3 grid((unsigned)ceil_div(waves, 4), (unsigned)ntypes);
                 if (sketch)
                     group_reduce_kernel<false><<<grid, 256, 0, st>>>(
-                        blk.p, nk, nullptr, empty_nan, b0, nb, k0, nk, upper ? 1 : 0, lab.as<int32_t>(), s->nsets,
-                        nitems, nseg, acc.as<unsigned long long>());
+                        blk.p, nk, nullptr, nullptr, empty_nan, b0, nb, k0, nk, upper ? 1 : 0, lab.as<int32_t>(),
+                        s->nsets, lab.as<int32_t>(), s->nsets, nitems, nseg, acc.as<unsigned long long>());
                 else
                     group_reduce_kernel<true><<<grid, 256, 0, st>>>(
-                        blk.p, nk, s->off.as<int64_t>(), empty_nan, b0, nb, k0, nk, upper ? 1 : 0,
-                        lab.as<int32_t>(), s->nsets, nitems, nseg, acc.as<unsigned long long>());
+                        blk.p, nk, s->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan, b0, nb, k0, nk, upper ? 1 : 0,
+                        lab.as<int32_t>(), s->nsets, lab.as<int32_t>(), s->nsets, nitems, nseg,
+                        acc.as<unsigned long long>());
                 GD_HIP(hipGetLastError());
                 if (timed) {
                     GD_HIP(hipEventRecord(ev[2], st));
@@ -293,31 +346,7 @@ void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t 
         ctx->group_reduce_ms = reduce_ms;
     }
 
-    // carries of the digit slots, min / max from their patterns, mean and sdev
-    for (int t = 0; t < ntypes; t++) {
-        const unsigned long long* g = h.data() + (size_t)t * kTypeSlots;
-        for (int k = 0; k < 2; k++) {
-            const unsigned long long* w = g + k * kSideSlots;
-            gdist_group_side o;
-            std::memset(&o, 0, sizeof(o));
-            o.n = (int64_t)w[0];
-            o.ones = (int64_t)w[1];
-            o.nans = (int64_t)w[2];
-            gstats::U256 S, Q;
-            for (int d = 0; d < 4; d++) gstats::add_digit(S, w[3 + d], d);
-            for (int d = 0; d < 6; d++) gstats::add_digit(Q, w[7 + d], d);
-            if (S.w[2] | S.w[3] | Q.w[3]) throw Error(GDIST_EDEVICE, "group statistics: a sum exceeds its limbs");
-            o.sum[0] = S.w[0];
-            o.sum[1] = S.w[1];
-            for (int i = 0; i < 3; i++) o.sumsq[i] = Q.w[i];
-            const unsigned long long mn = ~w[13], mx = w[14];
-            std::memcpy(&o.min, &mn, 8);
-            std::memcpy(&o.max, &mx, 8);
-            gstats::finish(&o);
-            out[2 * t + k] = o;
-        }
-        bad[t] = (int64_t)g[2 * kSideSlots];
-    }
+    group_finish(h.data(), ntypes, out, bad);
 }
 
 }  // namespace gdist

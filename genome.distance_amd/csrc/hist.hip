@@ -47,13 +47,17 @@ constexpr int kMaxSlots = 2 * kMaxBuckets + 3;
 // blockIdx.y (labels == nullptr: one series of every pair). A work item is
 // (row, segment of kSegCols columns); wave w of the launch takes the items
 // w, w + waves, ...
+//  The row's size and label come from roff / rlabels ([.][nrsets]), the
+//  column's from coff / clabels ([.][ncsets]): one collection passes the same
+//  pointers twice, the cross calls (cross.hip) the queries' and the subjects'.
 //  FromCounts: src is I (int32, row a / column b at src[a * ld + b]) and d is
 //  the Java expression of epilogue_kernel (bitset.hip), closest_select_kernel
 //  and group_reduce_kernel, fp64, no contraction; else src is D (double).
 template <bool FromCounts>
 __global__ __launch_bounds__(256) void hist_kernel(
-    const void* __restrict__ src, int64_t ld, const int64_t* __restrict__ off, int empty_nan, int64_t q0,
-    int64_t nrows, int64_t c0, int64_t nc, int upper, const int32_t* __restrict__ labels, int64_t nsets,
+    const void* __restrict__ src, int64_t ld, const int64_t* __restrict__ roff, const int64_t* __restrict__ coff,
+    int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, int upper,
+    const int32_t* __restrict__ rlabels, int64_t nrsets, const int32_t* __restrict__ clabels, int64_t ncsets,
     int64_t nitems, int64_t nseg, const double* __restrict__ edges, int E, unsigned long long* __restrict__ acc) {
 #pragma clang fp contract(off)
     __shared__ double edge[GDIST_HIST_MAX_EDGES];
@@ -61,7 +65,8 @@ __global__ __launch_bounds__(256) void hist_kernel(
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int type = blockIdx.y;
     const int nb = E + 1, nslots = 2 * nb + 3;
-    const int32_t* lab = labels ? labels + (int64_t)type * nsets : nullptr;
+    const int32_t* rlab = rlabels ? rlabels + (int64_t)type * nrsets : nullptr;
+    const int32_t* clab = clabels ? clabels + (int64_t)type * ncsets : nullptr;
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     for (int i = threadIdx.x; i < E; i += 256) edge[i] = edges[i];
     for (int i = threadIdx.x; i < nslots; i += 256) cnt[i] = 0;
@@ -77,9 +82,9 @@ __global__ __launch_bounds__(256) void hist_kernel(
         const int64_t bend = min(nc, b0 + (int64_t)kSegCols);
         const int64_t q = q0 + a;
         if (upper && c0 + bend - 1 <= q) continue;   // wholly on or left of the diagonal (wave-uniform)
-        const int32_t la = lab ? lab[q] : 0;
+        const int32_t la = rlab ? rlab[q] : 0;
         int64_t na = 0;
-        if (FromCounts) na = off[q + 1] - off[q];
+        if (FromCounts) na = roff[q + 1] - roff[q];
         const int32_t* Ir = static_cast<const int32_t*>(src) + a * ld;
         const double* Dr = static_cast<const double*>(src) + a * ld;
         for (int64_t bb = b0 + lane; bb < bend; bb += 64 * kBatch) {
@@ -97,10 +102,10 @@ __global__ __launch_bounds__(256) void hist_kernel(
                 nbv[u] = 0;
                 dv[u] = 0.0;
                 if (ok[u]) {
-                    lbv[u] = lab ? lab[j] : 0;
+                    lbv[u] = clab ? clab[j] : 0;
                     if (FromCounts) {
                         iv[u] = Ir[b];
-                        nbv[u] = off[j + 1] - off[j];
+                        nbv[u] = coff[j + 1] - coff[j];
                     } else {
                         dv[u] = Dr[b];
                     }
@@ -157,7 +162,47 @@ __global__ __launch_bounds__(256) void hist_kernel(
     }
 }
 
+// enough waves for ~4 a SIMD, and never more than kMaxItemsPerWave items a
+// wave (the kernel's overflow bound)
+dim3 hist_grid(const gdist_ctx* ctx, int64_t nrows, int64_t nc, int passes) {
+    const int64_t nitems = nrows * ceil_div(nc, kSegCols);
+    const int64_t waves =
+        std::max(std::min<int64_t>(nitems, (int64_t)ctx->cus * 16), ceil_div(nitems, kMaxItemsPerWave));
+    return dim3((unsigned)ceil_div(waves, 4), (unsigned)passes);
+}
+
 }  // namespace
+
+size_t hist_slots(int nedges, int ntypes) { return (size_t)std::max(1, ntypes) * ((size_t)2 * (nedges + 1) + 3); }
+
+void hist_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
+                 int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, int ntypes,
+                 const int32_t* d_rlab, int64_t nrsets, const int32_t* d_clab, int64_t ncsets, const double* d_edges,
+                 int nedges, unsigned long long* d_acc) {
+    const dim3 grid = hist_grid(ctx, nrows, nc, std::max(1, ntypes));
+    const int64_t nseg = ceil_div(nc, kSegCols);
+    hist_kernel<true><<<grid, 256, 0, ctx->stream>>>(d_I, ld, d_roff, d_coff, empty_nan, q0, nrows, c0, nc, 0,
+                                                     ntypes ? d_rlab : nullptr, nrsets, ntypes ? d_clab : nullptr,
+                                                     ncsets, nrows * nseg, nseg, d_edges, nedges, d_acc);
+    GD_HIP(hipGetLastError());
+}
+
+void hist_finish(const unsigned long long* h, int nedges, int ntypes, int64_t* counts, int64_t* nans, int64_t* bad) {
+    // series 2 t / 2 t + 1 of grouping t; without labels the one series is
+    // the in side of the single pass (every label reads as 0)
+    const int nb = nedges + 1, passes = std::max(1, ntypes);
+    const size_t tslots = (size_t)2 * nb + 3;
+    const int sides = ntypes ? 2 : 1;
+    for (int t = 0; t < passes; t++) {
+        const unsigned long long* g = h + (size_t)t * tslots;
+        for (int k = 0; k < sides; k++) {
+            int64_t* row = counts + (size_t)(sides * t + k) * nb;
+            for (int b = 0; b < nb; b++) row[b] = (int64_t)g[(size_t)k * nb + b];
+            nans[sides * t + k] = (int64_t)g[2 * nb + k];
+        }
+        if (ntypes) bad[t] = (int64_t)g[2 * nb + 2];
+    }
+}
 
 void histogram(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
                unsigned flags, int nedges, const double* edges, int ntypes, const int32_t* labels, int64_t* counts,
@@ -205,21 +250,18 @@ void histogram(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0
                     sorted_matrix(ctx, s, b0, b1, k0, k1, false, blk.as<int32_t>(), nk);
                 }
                 if (timed) GD_HIP(hipEventRecord(ev[1], st));
-                // enough waves for ~4 a SIMD, and never more than
-                // kMaxItemsPerWave items a wave (the kernel's overflow bound)
+                const dim3 grid = hist_grid(ctx, nbr, nk, passes);
                 const int64_t nseg = ceil_div(nk, kSegCols), nitems = nbr * nseg;
-                const int64_t waves = std::max(std::min<int64_t>(nitems, (int64_t)ctx->cus * 16),
-                                               ceil_div(nitems, kMaxItemsPerWave));
-                const dim3 grid((unsigned)ceil_div(waves, 4), (unsigned)passes);
                 const int32_t* dl = ntypes ? lab.as<int32_t>() : nullptr;
                 if (sketch)
                     hist_kernel<false><<<grid, 256, 0, st>>>(
-                        blk.p, nk, nullptr, empty_nan, b0, nbr, k0, nk, upper ? 1 : 0, dl, s->nsets, nitems, nseg,
-                        edg.as<double>(), nedges, acc.as<unsigned long long>());
+                        blk.p, nk, nullptr, nullptr, empty_nan, b0, nbr, k0, nk, upper ? 1 : 0, dl, s->nsets, dl,
+                        s->nsets, nitems, nseg, edg.as<double>(), nedges, acc.as<unsigned long long>());
                 else
                     hist_kernel<true><<<grid, 256, 0, st>>>(
-                        blk.p, nk, s->off.as<int64_t>(), empty_nan, b0, nbr, k0, nk, upper ? 1 : 0, dl, s->nsets,
-                        nitems, nseg, edg.as<double>(), nedges, acc.as<unsigned long long>());
+                        blk.p, nk, s->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan, b0, nbr, k0, nk,
+                        upper ? 1 : 0, dl, s->nsets, dl, s->nsets, nitems, nseg, edg.as<double>(), nedges,
+                        acc.as<unsigned long long>());
                 GD_HIP(hipGetLastError());
                 if (timed) {
                     GD_HIP(hipEventRecord(ev[2], st));
@@ -239,18 +281,7 @@ void histogram(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0
         ctx->hist_reduce_ms = reduce_ms;
     }
 
-    // series 2 t / 2 t + 1 of grouping t; without labels the one series is
-    // the in side of the single pass (every label reads as 0)
-    const int sides = ntypes ? 2 : 1;
-    for (int t = 0; t < passes; t++) {
-        const unsigned long long* g = h.data() + (size_t)t * tslots;
-        for (int k = 0; k < sides; k++) {
-            int64_t* row = counts + (size_t)(sides * t + k) * nb;
-            for (int b = 0; b < nb; b++) row[b] = (int64_t)g[(size_t)k * nb + b];
-            nans[sides * t + k] = (int64_t)g[2 * nb + k];
-        }
-        if (ntypes) bad[t] = (int64_t)g[2 * nb + 2];
-    }
+    hist_finish(h.data(), nedges, ntypes, counts, nans, bad);
 }
 
 }  // namespace gdist

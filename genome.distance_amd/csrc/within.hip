@@ -48,11 +48,15 @@ constexpr int kSegCols = 64 * kLoads * 2;    // columns of a tile
 // The test of one (row q, column c0 + b) cell, b < nc.
 //  FromCounts: d is the Java expression of epilogue_kernel (bitset.hip) and
 //  closest_select_kernel from I, fp64, no contraction; else d is loaded from D.
+//  The row's size comes from roff, the column's from coff: one collection
+//  passes the same pointer twice, gdist_cross_within the queries' and the
+//  subjects' (with keep_self and without upper: q and j index different
+//  collections there and their comparison decides nothing).
 template <bool FromCounts>
 struct RowView {
     const int32_t* Ir;
     const double* Dr;
-    const int64_t* off;
+    const int64_t* coff;
     int64_t na, q, c0;
     int empty_nan, keep_self, upper;
     double max_dist;
@@ -62,7 +66,7 @@ struct RowView {
         if (!FromCounts) return Dr[b];
         const int64_t j = c0 + b;
         const int64_t inter = Ir[b];
-        const int64_t nb = off[j + 1] - off[j];
+        const int64_t nb = coff[j + 1] - coff[j];
         if (inter > 0) {
             const double uni = (double)(na + nb - inter);
             return 1.0 - (double)inter / uni;
@@ -76,16 +80,16 @@ struct RowView {
 };
 
 template <bool FromCounts>
-__device__ __forceinline__ RowView<FromCounts> row_view(const void* src, int64_t ld, const int64_t* off,
-                                                       int empty_nan, int64_t q0, int64_t a, int64_t c0,
-                                                       int keep_self, int upper, double max_dist) {
+__device__ __forceinline__ RowView<FromCounts> row_view(const void* src, int64_t ld, const int64_t* roff,
+                                                       const int64_t* coff, int empty_nan, int64_t q0, int64_t a,
+                                                       int64_t c0, int keep_self, int upper, double max_dist) {
     RowView<FromCounts> v;
     v.Ir = static_cast<const int32_t*>(src) + a * ld;
     v.Dr = static_cast<const double*>(src) + a * ld;
-    v.off = off;
+    v.coff = coff;
     v.q = q0 + a;
     v.na = 0;
-    if (FromCounts) v.na = off[v.q + 1] - off[v.q];
+    if (FromCounts) v.na = roff[v.q + 1] - roff[v.q];
     v.c0 = c0;
     v.empty_nan = empty_nan;
     v.keep_self = keep_self;
@@ -99,16 +103,16 @@ __device__ __forceinline__ RowView<FromCounts> row_view(const void* src, int64_t
 // nseg + segment; tile_count[it] = its survivors.
 template <bool FromCounts>
 __global__ __launch_bounds__(256) void within_count_kernel(
-    const void* __restrict__ src, int64_t ld, const int64_t* __restrict__ off, int empty_nan, int64_t q0,
-    int64_t c0, int64_t nc, int keep_self, int upper, double max_dist, int64_t ntiles, int64_t nseg,
-    int32_t* __restrict__ tile_count) {
+    const void* __restrict__ src, int64_t ld, const int64_t* __restrict__ roff, const int64_t* __restrict__ coff,
+    int empty_nan, int64_t q0, int64_t c0, int64_t nc, int keep_self, int upper, double max_dist, int64_t ntiles,
+    int64_t nseg, int32_t* __restrict__ tile_count) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t it = (int64_t)blockIdx.x * 4 + wave;
     if (it >= ntiles) return;   // no workgroup barrier below: a wave may leave alone
     const int64_t a = it / nseg, b0 = (it - a * nseg) * kSegCols;
     const int64_t bend = min(nc, b0 + (int64_t)kSegCols);
     const RowView<FromCounts> v =
-        row_view<FromCounts>(src, ld, off, empty_nan, q0, a, c0, keep_self, upper, max_dist);
+        row_view<FromCounts>(src, ld, roff, coff, empty_nan, q0, a, c0, keep_self, upper, max_dist);
     int cnt = 0;
     if (!(upper && c0 + bend - 1 <= v.q)) {   // else wholly on or left of the diagonal (wave-uniform)
         for (int64_t g0 = b0; g0 < bend; g0 += 64 * kLoads) {
@@ -137,9 +141,9 @@ __global__ void within_row_base_kernel(const int64_t* __restrict__ tile_base, in
 // limit goes to col_out[p] / d_out[p] (the step's staging buffers).
 template <bool FromCounts>
 __global__ __launch_bounds__(256) void within_write_kernel(
-    const void* __restrict__ src, int64_t ld, const int64_t* __restrict__ off, int empty_nan, int64_t q0,
-    int64_t c0, int64_t nc, int keep_self, int upper, double max_dist, int64_t ntiles, int64_t nseg,
-    const int64_t* __restrict__ tile_base, int64_t limit, int64_t* __restrict__ col_out,
+    const void* __restrict__ src, int64_t ld, const int64_t* __restrict__ roff, const int64_t* __restrict__ coff,
+    int empty_nan, int64_t q0, int64_t c0, int64_t nc, int keep_self, int upper, double max_dist, int64_t ntiles,
+    int64_t nseg, const int64_t* __restrict__ tile_base, int64_t limit, int64_t* __restrict__ col_out,
     double* __restrict__ d_out) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t it = (int64_t)blockIdx.x * 4 + wave;
@@ -149,7 +153,7 @@ __global__ __launch_bounds__(256) void within_write_kernel(
     const int64_t a = it / nseg, b0 = (it - a * nseg) * kSegCols;
     const int64_t bend = min(nc, b0 + (int64_t)kSegCols);
     const RowView<FromCounts> v =
-        row_view<FromCounts>(src, ld, off, empty_nan, q0, a, c0, keep_self, upper, max_dist);
+        row_view<FromCounts>(src, ld, roff, coff, empty_nan, q0, a, c0, keep_self, upper, max_dist);
     for (int64_t g0 = b0; g0 < bend; g0 += 64 * kLoads) {
         double dv[kLoads];
 #pragma unroll
@@ -187,6 +191,31 @@ int64_t within_rows(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem) {
     int64_t R = std::max<int64_t>(1, std::min<int64_t>(4096, (int64_t(1) << 30) / per_row));
     if (ctx->has_option(OPT_CLOSEST_ROWS)) R = std::max<int64_t>(1, ctx->option(OPT_CLOSEST_ROWS, R));
     return std::min<int64_t>(R, std::max<int64_t>(nr, 1));
+}
+
+int64_t within_tiles(int64_t nrows, int64_t nc) { return nrows * ceil_div(nc, kSegCols); }
+
+void within_count_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
+                         int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, double max_dist,
+                         int32_t* d_tcount, int64_t* d_tbase, int64_t* d_rbase, DevBuf& scan_tmp) {
+    hipStream_t st = ctx->stream;
+    const int64_t nseg = ceil_div(nc, kSegCols), ntiles = nrows * nseg;
+    within_count_kernel<true><<<(unsigned)ceil_div(ntiles, 4), 256, 0, st>>>(
+        d_I, ld, d_roff, d_coff, empty_nan, q0, c0, nc, 1, 0, max_dist, ntiles, nseg, d_tcount);
+    GD_HIP(hipGetLastError());
+    // ntiles + 1 elements: the step's total lands at d_tbase[ntiles]
+    scan_counts(st, d_tcount, d_tbase, (size_t)ntiles + 1, scan_tmp);
+    within_row_base_kernel<<<(unsigned)ceil_div(nrows + 1, 256), 256, 0, st>>>(d_tbase, nseg, nrows, d_rbase);
+    GD_HIP(hipGetLastError());
+}
+
+void within_write_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
+                         int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, double max_dist,
+                         const int64_t* d_tbase, int64_t fit, int64_t* d_col, double* d_d) {
+    const int64_t nseg = ceil_div(nc, kSegCols), ntiles = nrows * nseg;
+    within_write_kernel<true><<<(unsigned)ceil_div(ntiles, 4), 256, 0, ctx->stream>>>(
+        d_I, ld, d_roff, d_coff, empty_nan, q0, c0, nc, 1, 0, max_dist, ntiles, nseg, d_tbase, fit, d_col, d_d);
+    GD_HIP(hipGetLastError());
 }
 
 // method: SORTED or BITSET (resolved by the caller); ignored for sketches.
@@ -248,11 +277,11 @@ void within(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, i
         const unsigned grid = (unsigned)ceil_div(ntiles, 4);
         const int64_t* off = sketch ? nullptr : s->off.as<int64_t>();
         if (sketch)
-            within_count_kernel<false><<<grid, 256, 0, st>>>(blk.p, nk, off, empty_nan, b0, k0, nk, keep_self,
+            within_count_kernel<false><<<grid, 256, 0, st>>>(blk.p, nk, off, off, empty_nan, b0, k0, nk, keep_self,
                                                              upper ? 1 : 0, max_dist, ntiles, nseg,
                                                              tcount.as<int32_t>());
         else
-            within_count_kernel<true><<<grid, 256, 0, st>>>(blk.p, nk, off, empty_nan, b0, k0, nk, keep_self,
+            within_count_kernel<true><<<grid, 256, 0, st>>>(blk.p, nk, off, off, empty_nan, b0, k0, nk, keep_self,
                                                             upper ? 1 : 0, max_dist, ntiles, nseg,
                                                             tcount.as<int32_t>());
         GD_HIP(hipGetLastError());
@@ -272,11 +301,11 @@ void within(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, i
             if (timed) GD_HIP(hipEventRecord(ev[3], st));
             if (sketch)
                 within_write_kernel<false><<<grid, 256, 0, st>>>(
-                    blk.p, nk, off, empty_nan, b0, k0, nk, keep_self, upper ? 1 : 0, max_dist, ntiles, nseg,
+                    blk.p, nk, off, off, empty_nan, b0, k0, nk, keep_self, upper ? 1 : 0, max_dist, ntiles, nseg,
                     tbase.as<int64_t>(), fit, sc.as<int64_t>(), sd.as<double>());
             else
                 within_write_kernel<true><<<grid, 256, 0, st>>>(
-                    blk.p, nk, off, empty_nan, b0, k0, nk, keep_self, upper ? 1 : 0, max_dist, ntiles, nseg,
+                    blk.p, nk, off, off, empty_nan, b0, k0, nk, keep_self, upper ? 1 : 0, max_dist, ntiles, nseg,
                     tbase.as<int64_t>(), fit, sc.as<int64_t>(), sd.as<double>());
             GD_HIP(hipGetLastError());
             if (timed) GD_HIP(hipEventRecord(ev[4], st));

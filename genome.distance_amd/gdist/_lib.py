@@ -160,6 +160,12 @@ _SIGS = {
     "gdist_cross_matrix": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64, _i64, _i64, _u32, _i32p, _dblp, _i64]),
     "gdist_cross_closest": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64, _i64, _i64, _u32, C.c_int, _dbl, _i64p, _dblp,
                                       _i32p]),
+    "gdist_cross_within": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64, _i64, _i64, _u32, _dbl, _i64, _i64p, _i64p, _dblp,
+                                     _i64p]),
+    "gdist_cross_group_stats": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64, _i64, _i64, _u32, C.c_int, _i32p, _i32p, _vp,
+                                          _i64p]),
+    "gdist_cross_histogram": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64, _i64, _i64, _u32, C.c_int, _dblp, C.c_int,
+                                        _i32p, _i32p, _i64p, _i64p, _i64p]),
     "gdist_ctx_cross_info": (C.c_int, [_ctxp, _dblp, _dblp, _i64p]),
     "gdist_histogram": (C.c_int, [_ctxp, _setp, _i64, _i64, _i64, _i64, C.c_int, _u32, C.c_int, _dblp, C.c_int, _i32p,
                                   _i64p, _i64p, _i64p]),

@@ -151,10 +151,12 @@ class Context:
 
     def cross_info(self) -> tuple[float, float, int]:
         """(join kernel ms, select kernel ms, units) of the context's last
-        cross_matrix() / cross_closest() call (gdist_ctx_cross_info): the times
-        are summed over the steps and -1 unless option time_kernels = 1 (after
-        cross_matrix the second one is the distance epilogue); units are the
-        (query row, column block, segment range) work units launched."""
+        cross_*() call (gdist_ctx_cross_info): the times are summed over the
+        steps and -1 unless option time_kernels = 1. The second one is the
+        kernels that consume the counts: the select (cross_closest), the
+        distance epilogue (cross_matrix), count + scan + write (cross_within),
+        the reduce (cross_group_stats), the histogram kernel (cross_histogram).
+        units are the (query row, column block, segment range) work units launched."""
         j, s, u = C.c_double(), C.c_double(), C.c_int64()
         L.check(L.lib.gdist_ctx_cross_info(self.h, C.byref(j), C.byref(s), C.byref(u)))
         return j.value, s.value, u.value
@@ -1011,6 +1013,106 @@ class KmerSets(_Handle):
                                           float(max_dist), L.ptr(bi, C.c_int64), L.ptr(bd, C.c_double),
                                           L.ptr(bc, C.c_int32)))
         return idx, d, cnt
+
+    @staticmethod
+    def _cross_labels(labels, n: int, what: str) -> np.ndarray:
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.ndim == 1:
+            lab = lab[None, :]
+        if lab.ndim != 2 or lab.shape[1] != n:
+            raise ValueError(f"{what} must be [T, {n}] or [{n}], not {list(lab.shape)}")
+        if not 1 <= lab.shape[0] <= L.GROUP_MAX_TYPES:
+            raise ValueError(f"{lab.shape[0]} groupings: 1 .. {L.GROUP_MAX_TYPES} a call")
+        return lab
+
+    def cross_within(self, queries: "KmerSets", max_dist: float, rows: tuple[int, int] | None = None,
+                     cols: tuple[int, int] | None = None, empty_nan: bool = False, capacity: int | None = None):
+        """Every (query, resident set) pair within a distance (gdist_cross_within):
+        the pairs (i, j) of `rows` of `queries` x `cols` of this collection with
+        Jaccard distance <= max_dist, row ascending then column ascending, as
+        CSR: (rowptr int64[nr + 1], cols int64[m], d float64[m]); the columns
+        are indices of this collection and none is left out as the query
+        itself. capacity None: the complete list (a guess, then a second call
+        when the total exceeds it, as within()); a number: at most that many
+        entries, rowptr still the full counts. d is cross_matrix()'s D bit for
+        bit. This collection is only read and nothing is packed again."""
+        r0, r1 = rows or (0, len(queries))
+        c0, c1 = cols or (0, len(self))
+        nr = max(r1 - r0, 0)
+        fl = L.EMPTY_NAN if empty_nan else 0
+        rowptr = np.zeros(nr + 1, dtype=np.int64)
+        total = C.c_int64(0)
+        cap = int(capacity) if capacity is not None else max(nr, 1) * self.WITHIN_GUESS_PER_ROW
+        while True:
+            # non-empty buffers behind empty results: the library is never handed a null output
+            col = np.zeros(max(cap, 1), dtype=np.int64)
+            d = np.zeros(max(cap, 1), dtype=np.float64)
+            L.check(L.lib.gdist_cross_within(self.ctx.h, queries.h, self.h, r0, r1, c0, c1, fl, float(max_dist), cap,
+                                             L.ptr(rowptr, C.c_int64), L.ptr(col, C.c_int64), L.ptr(d, C.c_double),
+                                             C.byref(total)))
+            if capacity is not None or total.value <= cap:
+                m = min(total.value, cap)
+                return rowptr, col[:m], d[:m]
+            cap = total.value
+
+    def cross_group_stats(self, queries: "KmerSets", qlabels, slabels, rows: tuple[int, int] | None = None,
+                          cols: tuple[int, int] | None = None, empty_nan: bool = False) -> GroupStats:
+        """In-group / out-group summary of the distances of `queries` (rows)
+        against this resident collection (cols) (gdist_cross_group_stats):
+        qlabels int32 [T, len(queries)] and slabels int32 [T, len(self)] (or
+        1-d for one grouping), the group of every set (< 0: none, the pair is
+        counted as bad). Every cell of the rectangle counts. The result merges
+        with any other GroupStats; this collection is only read."""
+        ql = self._cross_labels(qlabels, len(queries), "qlabels")
+        sl = self._cross_labels(slabels, len(self), "slabels")
+        if ql.shape[0] != sl.shape[0]:
+            raise ValueError(f"{ql.shape[0]} query groupings but {sl.shape[0]} subject groupings")
+        T = ql.shape[0]
+        r0, r1 = rows or (0, len(queries))
+        c0, c1 = cols or (0, len(self))
+        sides, bad = (L.GroupSide * (2 * T))(), (C.c_int64 * T)()
+        qb = ql if ql.size else np.zeros(1, dtype=np.int32)
+        sb = sl if sl.size else np.zeros(1, dtype=np.int32)
+        L.check(L.lib.gdist_cross_group_stats(self.ctx.h, queries.h, self.h, r0, r1, c0, c1,
+                                              L.EMPTY_NAN if empty_nan else 0, T, L.ptr(qb, C.c_int32),
+                                              L.ptr(sb, C.c_int32), C.addressof(sides), bad))
+        return GroupStats(sides, bad)
+
+    def cross_histogram(self, queries: "KmerSets", edges, qlabels=None, slabels=None,
+                        rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,
+                        empty_nan: bool = False) -> Histogram:
+        """How the distances of `queries` (rows) against this resident
+        collection (cols) are distributed (gdist_cross_histogram): edges and
+        buckets as histogram(); without labels one series of every pair, with
+        qlabels / slabels (as cross_group_stats) an in-group and an out-group
+        series per grouping. Every cell of the rectangle counts; histograms of
+        disjoint rectangles add. This collection is only read."""
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        if not 1 <= len(e) <= L.HIST_MAX_EDGES:
+            raise ValueError(f"{len(e)} edges: 1 .. {L.HIST_MAX_EDGES} a call")
+        if (qlabels is None) != (slabels is None):
+            raise ValueError("qlabels and slabels come together")
+        T, qb, sb = 0, None, None
+        if qlabels is not None:
+            ql = self._cross_labels(qlabels, len(queries), "qlabels")
+            sl = self._cross_labels(slabels, len(self), "slabels")
+            if ql.shape[0] != sl.shape[0]:
+                raise ValueError(f"{ql.shape[0]} query groupings but {sl.shape[0]} subject groupings")
+            T = ql.shape[0]
+            qb = ql if ql.size else np.zeros(1, dtype=np.int32)
+            sb = sl if sl.size else np.zeros(1, dtype=np.int32)
+        r0, r1 = rows or (0, len(queries))
+        c0, c1 = cols or (0, len(self))
+        S = 2 * T if T else 1
+        counts = np.zeros((S, len(e) + 1), dtype=np.int64)
+        nans = np.zeros(S, dtype=np.int64)
+        bad = np.zeros(max(T, 1), dtype=np.int64)
+        L.check(L.lib.gdist_cross_histogram(self.ctx.h, queries.h, self.h, r0, r1, c0, c1,
+                                            L.EMPTY_NAN if empty_nan else 0, len(e), L.ptr(e, C.c_double), T,
+                                            L.ptr(qb, C.c_int32) if T else None, L.ptr(sb, C.c_int32) if T else None,
+                                            L.ptr(counts, C.c_int64), L.ptr(nans, C.c_int64),
+                                            L.ptr(bad, C.c_int64) if T else None))
+        return Histogram(e, counts, nans, bad[:T])
 
     def row_query(self, q: int, cols: Iterable[int], mode: int = L.QUERY_ALL, t: float = 1.0):
         cl = np.ascontiguousarray(np.fromiter(cols, dtype=np.int64))

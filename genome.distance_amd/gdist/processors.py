@@ -7,6 +7,7 @@ row-block / row-query calls on the device:
   fasta_distance   FastaDistanceProcessor  (fastaDist)  FastaDistanceProcessor.java:84-194
   fasta_close_pairs  the fastaDist lines with distance <= max_dist (KmerSets.within)
   genome_distance  GenomeProcessor         (genomes)    GenomeProcessor.java:74-150
+  genomes_against  the same table over a resident base collection (KmerSets.cross_*)
   fasta_reps       FastaDistanceRepsProcessor (fastaReps) FastaDistanceRepsProcessor.java:58-149
   distance_reps    DistanceRepsProcessor   (distReps)   DistanceRepsProcessor.java:140-275
   width_processor  WidthProcessor          (width)      WidthProcessor.java:88-208
@@ -454,6 +455,60 @@ def find_genomes(db: KmerSets, subjects: Sequence[Genome], queries: Iterable[Gen
         flush(group)
     # the counters of the closing log line: FindProcessor.java:119
     return found, fail
+
+
+def genomes_against(db: KmerSets, base: Sequence[Genome], comparisons: Iterable[Genome], out: TextIO,
+                    max_dist: float = 0.9, within: bool = False, batch: int = 64) -> int:
+    """The `genomes` table over a resident base collection: `db` holds the kmer
+    sets of `base` (set j is base[j]) and stays on the device as it is, as the
+    reference pre-loads its base genomes and then compares every comparison
+    genome against them (GenomeProcessor.java:100-111,140). The comparison
+    genomes are packed `batch` at a time with the database's k and pack flags;
+    the base genomes are never packed again. The header and the lines are
+    those of genome_distance for the same genomes: every pair
+    (KmerSets.cross_matrix), or with within=True only the pairs with distance
+    <= max_dist, the documented -m filter (GenomeProcessor.java:35), from
+    KmerSets.cross_within. Returns the lines written."""
+    if max_dist <= 0.0 or max_dist > 1.0:
+        raise ParseFailureException("Maximum distance must be > 0 and <= 1.")    # GenomeProcessor.java:89-90
+    if len(db) != len(base):
+        raise ValueError(f"the database holds {len(db)} sets but {len(base)} base genomes were named")
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    out.write("genome1\tgenome2\tdistance\n")                                    # GenomeProcessor.java:121
+    if not base:
+        return 0
+    n = 0
+
+    def flush(group):
+        nonlocal n
+        qs = db.pack_like([g.kmer_text() for g in group])
+        try:
+            if within:
+                rowptr, cols, d = db.cross_within(qs, max_dist)
+            else:
+                _, D = db.cross_matrix(qs, want_I=False)
+        finally:
+            qs.free()
+        for a, g in enumerate(group):
+            if within:
+                for p in range(rowptr[a], rowptr[a + 1]):
+                    out.write(f"{g.id}\t{base[cols[p]].id}\t{java_double(d[p])}\n")
+                n += int(rowptr[a + 1] - rowptr[a])
+            else:
+                for i, bg in enumerate(base):                                     # GenomeProcessor.java:143-144
+                    out.write(f"{g.id}\t{bg.id}\t{java_double(D[a, i])}\n")
+                n += len(base)
+
+    group = []
+    for g in comparisons:
+        group.append(g)
+        if len(group) >= batch:
+            flush(group)
+            group = []
+    if group:
+        flush(group)
+    return n
 
 
 def group_labels(ids: Sequence[str], groupings: dict) -> tuple[list[str], np.ndarray]:

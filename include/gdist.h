@@ -35,6 +35,12 @@
  *                          against the loaded genome database    FindProcessor.java:94-110, MashProcessor.java:150
  *   gdist_cross_matrix     the same queries x database rectangle
  *                          as counts and distances               GenomeProcessor.java:140
+ *   gdist_cross_within     the -m filter of comparison genomes
+ *                          against the pre-loaded base genomes   GenomeProcessor.java:35,140
+ *   gdist_cross_group_stats in / out-group summary of new genomes
+ *                          against the database                  DistanceCheckProcessor.java:200-223
+ *   gdist_cross_histogram  the bucket report of new genomes
+ *                          against the database                  TaxCheckProcessor.java:133-135
  *   gdist_group_stats      recordDistance over a distance table  GroupTypeSpec.java:77-95
  *                          in / out-group min, mean, sd, max     DistanceCheckProcessor.java:200-223
  *   gdist_histogram        new Distributor(0.0, 1.0, 50)         TaxCheckProcessor.java:93
@@ -606,10 +612,71 @@ int  gdist_cross_closest(gdist_ctx* ctx, const gdist_sets* queries, const gdist_
                          int64_t q0, int64_t q1, int64_t c0, int64_t c1, unsigned flags,
                          int n, double max_dist,
                          int64_t* idx_out, double* d_out, int32_t* count_out);
+
+/* gdist_cross_within, gdist_cross_group_stats, gdist_cross_histogram: the
+ * three table-free queries of one collection (gdist_within,
+ * gdist_group_stats, gdist_histogram) over the same rectangle of query rows
+ * [q0, q1) x subject columns [c0, c1), by the same join and under the same
+ * read-only rule for the subjects as the two calls above. Each takes its
+ * twin's arguments with `sets` replaced by `queries, subjects` and without
+ * `method`; column indices in the outputs (col_out) are subject indices. The
+ * only flag is GDIST_EMPTY_NAN: no column is "self" and there is no
+ * GDIST_UPPER_TRIANGLE, so every cell of the rectangle counts, and the same
+ * handle passed for both collections behaves as GDIST_CLOSEST_KEEP_SELF
+ * without GDIST_UPPER_TRIANGLE. Labels come per side: qlabels[t * nq + i] the
+ * group of query set i and slabels[t * ns + j] of subject set j under
+ * grouping t (nq, ns = all sets of the collections, whatever the ranges).
+ *
+ * Each call returns, bit for bit (rowptr, col, the d patterns, every field of
+ * gdist_group_side, counts, nans, bad), what its twin returns on
+ * C = gdist_sets_concat(subjects, queries) with GDIST_METHOD_SORTED for rows
+ * [ns+q0, ns+q1) x cols [c0, c1), the same flags (plus
+ * GDIST_CLOSEST_KEEP_SELF for within) and, for grouping t, the labels
+ * slabels[t] followed by qlabels[t]. Every other rule of the twins carries
+ * over: capacity may cut a row, capacity == 0 is the counting call and nothing
+ * at or past capacity is touched; disjoint row ranges of within concatenate;
+ * the group sums are exact limbs and merge through gdist_group_stats_merge;
+ * buckets are found by fp64 comparison only and the results of disjoint
+ * rectangles add element-wise.
+ *
+ * Walks. Group stats and histogram fold every (row block x column chunk) step
+ * into their accumulators (options "closest_rows" / "closest_cols"). Within
+ * needs a row's full width before it can compact in (row, column) order: row
+ * blocks sized as gdist_within sizes them ("closest_rows"; "closest_cols" is
+ * not read) over all of [c0, c1). No result depends on either option.
+ *
+ * An empty row or column range: GDIST_OK in the twin's empty form (rowptr all
+ * zero and total 0; every side in its n == 0 form and bad 0; every count
+ * zero). EINVAL, decided before any work with every output untouched: what
+ * gdist_cross_matrix refuses of the handles, ranges and flags, and each twin's
+ * own conditions: NaN max_dist, capacity < 0, null rowptr_out or total, null
+ * col_out or d_out with capacity > 0; ntypes outside 1..GDIST_GROUP_MAX_TYPES,
+ * null labels, out or bad; nedges outside 1..GDIST_HIST_MAX_EDGES, a NaN edge,
+ * edges not strictly ascending, ntypes outside 0..GDIST_GROUP_MAX_TYPES, null
+ * edges, counts_out or nans_out, null qlabels, slabels or bad_out with
+ * ntypes > 0. */
+int  gdist_cross_within(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects,
+                        int64_t q0, int64_t q1, int64_t c0, int64_t c1, unsigned flags,
+                        double max_dist, int64_t capacity,
+                        int64_t* rowptr_out /* q1 - q0 + 1 */, int64_t* col_out, double* d_out,
+                        int64_t* total);
+int  gdist_cross_group_stats(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects,
+                             int64_t q0, int64_t q1, int64_t c0, int64_t c1, unsigned flags, int ntypes,
+                             const int32_t* qlabels /* [ntypes][nq], host */,
+                             const int32_t* slabels /* [ntypes][ns], host */,
+                             gdist_group_side* out /* [ntypes][2]: in, out */, int64_t* bad /* [ntypes] */);
+int  gdist_cross_histogram(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects,
+                           int64_t q0, int64_t q1, int64_t c0, int64_t c1, unsigned flags,
+                           int nedges, const double* edges /* host, strictly ascending */,
+                           int ntypes, const int32_t* qlabels, const int32_t* slabels /* NULL when ntypes == 0 */,
+                           int64_t* counts_out /* [S][nedges + 1] */, int64_t* nans_out /* [S] */,
+                           int64_t* bad_out /* [ntypes]; may be NULL when ntypes == 0 */);
 /* last cross call: HIP-event time (ms, summed over the steps; -1 unless option
- * "time_kernels" = 1) of the join kernel and of the kernel that follows it
+ * "time_kernels" = 1) of the join kernel and of the kernels that follow it
  * (gdist_cross_closest: the select; gdist_cross_matrix: the distance
- * epilogue, 0 without D_out), and the work units launched */
+ * epilogue, 0 without D_out; gdist_cross_within: count, scan and write;
+ * gdist_cross_group_stats: the reduce; gdist_cross_histogram: the histogram
+ * kernel), and the work units launched */
 int  gdist_ctx_cross_info(gdist_ctx* ctx, double* join_ms, double* select_ms, int64_t* units);
 
 /* ---- distribution of the distances ------------------------------------- */
