@@ -187,93 +187,71 @@ void closest_blocks(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem, i
     *cols = W;
 }
 
-// one select step over counts whose rows and columns come from two collections
-// (cross.hip): every column may be a neighbour (no self to leave out)
-void closest_select_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff,
-                           const int64_t* d_coff, int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc,
-                           int n, int L, double max_dist, unsigned long long* st_d, uint32_t* st_c, int32_t* st_n,
-                           int last, int64_t* d_idx, double* d_d, int32_t* d_count) {
+SelfSource::SelfSource(gdist_ctx* c, const gdist_sets* sets, int m, unsigned flags)
+    : ctx(c), s(sets), method(m), mflags(flags & (GDIST_EMPTY_NAN | GDIST_SKETCH_JACCARD)) {
+    from_counts = s->kind != GDIST_SKETCH;
+    keep_self = (flags & GDIST_CLOSEST_KEEP_SELF) ? 1 : 0;
+    upper = (flags & GDIST_UPPER_TRIANGLE) ? 1 : 0;
+    empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
+    roff = coff = from_counts ? s->off.as<int64_t>() : nullptr;
+    nrsets = ncsets = s->nsets;
+    timed = ctx->option(OPT_TIME_KERNELS, 0) != 0;
+}
+
+void SelfSource::fill(int64_t b0, int64_t b1, int64_t k0, int64_t k1, void* blk) {
+    const int64_t nk = k1 - k0;
+    if (!from_counts) {
+        sketch_matrix(ctx, s, b0, b1, k0, k1, mflags, nullptr, static_cast<double*>(blk), nk);
+    } else if (method == GDIST_METHOD_BITSET) {
+        zero_counts(ctx, b0, b1, k0, k1, false, static_cast<int32_t*>(blk), nk);
+        bitset_matrix(ctx, s, b0, b1, k0, k1, false, static_cast<int32_t*>(blk), nk);
+    } else {
+        sorted_matrix(ctx, s, b0, b1, k0, k1, false, static_cast<int32_t*>(blk), nk);
+    }
+}
+
+// Ascending columns: the select's d < tau rule needs them. The lists are
+// empty when a row block's first chunk is selected (zeroed outside the timed
+// span: select_ms is the kernel's) and downloaded after its last.
+void closest_select(gdist_ctx* ctx, WalkSource& src, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int n,
+                    double max_dist, int64_t* idx_out, double* d_out, int32_t* count_out) {
+    hipStream_t st = ctx->stream;
+    int L = 128;
+    while (L < n) L <<= 1;
+    int64_t R, W;
+    closest_blocks(ctx, r1 - r0, c1 - c0, src.elem(), &R, &W);
+    Walk walk(ctx, src, R, W);
+    DevBuf sd((size_t)R * L * 8 + 8, st), sc((size_t)R * L * 4 + 4, st), sn((size_t)R * 4 + 4, st);
+    DevBuf oi((size_t)R * n * 8 + 8, st), od((size_t)R * n * 8 + 8, st), oc((size_t)R * 4 + 4, st);
     const size_t lds = (size_t)4 * 2 * L * 12;
-    closest_select_kernel<true><<<(unsigned)ceil_div(nrows, 4), 256, lds, ctx->stream>>>(
-        d_I, ld, d_roff, d_coff, empty_nan, q0, nrows, c0, nc, 1, n, L, max_dist, st_d, st_c, st_n, last, d_idx, d_d,
-        d_count);
-    GD_HIP(hipGetLastError());
+    GD_HIP(hipMemsetAsync(sn.p, 0, (size_t)R * 4, st));
+    walk.run(r0, r1, c0, c1, false, [&](const WalkStep& t) {
+        const auto kernel = src.from_counts ? closest_select_kernel<true> : closest_select_kernel<false>;
+        kernel<<<(unsigned)ceil_div(t.nb, 4), 256, lds, st>>>(
+            walk.blk.p, t.nk, src.roff, src.coff, src.empty_nan, t.b0, t.nb, t.k0, t.nk, src.keep_self, n, L, max_dist,
+            sd.as<unsigned long long>(), sc.as<uint32_t>(), sn.as<int32_t>(), t.last, oi.as<int64_t>(),
+            od.as<double>(), oc.as<int32_t>());
+        GD_HIP(hipGetLastError());
+    }, [&](const WalkStep& t) {
+        if (!t.last) return;
+        d2h(idx_out + (t.b0 - r0) * n, oi.p, (size_t)t.nb * n * 8, st);
+        d2h(d_out + (t.b0 - r0) * n, od.p, (size_t)t.nb * n * 8, st);
+        d2h(count_out + (t.b0 - r0), oc.p, (size_t)t.nb * 4, st);
+        if (t.b0 + t.nb < r1) GD_HIP(hipMemsetAsync(sn.p, 0, (size_t)R * 4, st));   // the next row block's
+    });
 }
 
 // method: SORTED or BITSET (resolved by the caller); ignored for sketches
 void closest(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
              unsigned flags, int n, double max_dist, int64_t* idx_out, double* d_out, int32_t* count_out) {
-    hipStream_t st = ctx->stream;
-    const int64_t nr = r1 - r0, nc = c1 - c0;
-    const bool sketch = s->kind == GDIST_SKETCH;
-    const size_t elem = sketch ? 8 : 4;
-    int L = 128;
-    while (L < n) L <<= 1;
-    int64_t R, W;
-    closest_blocks(ctx, nr, nc, elem, &R, &W);
-    const int keep_self = (flags & GDIST_CLOSEST_KEEP_SELF) ? 1 : 0;
-    const int empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
-    const unsigned mflags = flags & (GDIST_EMPTY_NAN | GDIST_SKETCH_JACCARD);
-    DevBuf blk((size_t)R * W * elem + 8, st);
-    DevBuf sd((size_t)R * L * 8 + 8, st), sc((size_t)R * L * 4 + 4, st), sn((size_t)R * 4 + 4, st);
-    DevBuf oi((size_t)R * n * 8 + 8, st), od((size_t)R * n * 8 + 8, st), oc((size_t)R * 4 + 4, st);
-    const size_t lds = (size_t)4 * 2 * L * 12;
+    SelfSource src(ctx, s, method, flags);
+    ctx->closest_matrix_ms = ctx->closest_select_ms = -1.0;
+    closest_select(ctx, src, r0, r1, c0, c1, n, max_dist, idx_out, d_out, count_out);
     // option time_kernels: the intersect (or sketch) kernels and the select
     // kernel of every step apart, HIP events on the stream (gdist_ctx_closest_timing)
-    const bool timed = ctx->option(OPT_TIME_KERNELS, 0) != 0;
-    ctx->closest_matrix_ms = ctx->closest_select_ms = -1.0;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    double matrix_ms = 0, select_ms = 0;
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() { for (int i = 0; i < 3; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-    } guard{ev};
-    if (timed) for (auto& e : ev) GD_HIP(hipEventCreate(&e));
-    for (int64_t b0 = r0; b0 < r1; b0 += R) {
-        const int64_t b1 = std::min(r1, b0 + R), nb = b1 - b0;
-        GD_HIP(hipMemsetAsync(sn.p, 0, (size_t)nb * 4, st));
-        for (int64_t k0 = c0; k0 < c1; k0 += W) {   // ascending columns: the select's d < tau rule needs it
-            const int64_t k1 = std::min(c1, k0 + W), nk = k1 - k0;
-            const int last = k1 == c1 ? 1 : 0;
-            if (timed) GD_HIP(hipEventRecord(ev[0], st));
-            if (sketch) {
-                sketch_matrix(ctx, s, b0, b1, k0, k1, mflags, nullptr, blk.as<double>(), nk);
-            } else if (method == GDIST_METHOD_BITSET) {
-                zero_counts(ctx, b0, b1, k0, k1, false, blk.as<int32_t>(), nk);
-                bitset_matrix(ctx, s, b0, b1, k0, k1, false, blk.as<int32_t>(), nk);
-            } else {
-                sorted_matrix(ctx, s, b0, b1, k0, k1, false, blk.as<int32_t>(), nk);
-            }
-            if (timed) GD_HIP(hipEventRecord(ev[1], st));
-            const unsigned grid = (unsigned)ceil_div(nb, 4);
-            if (sketch)
-                closest_select_kernel<false><<<grid, 256, lds, st>>>(
-                    blk.p, nk, nullptr, nullptr, empty_nan, b0, nb, k0, nk, keep_self, n, L, max_dist,
-                    sd.as<unsigned long long>(), sc.as<uint32_t>(), sn.as<int32_t>(), last, oi.as<int64_t>(),
-                    od.as<double>(), oc.as<int32_t>());
-            else
-                closest_select_kernel<true><<<grid, 256, lds, st>>>(
-                    blk.p, nk, s->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan, b0, nb, k0, nk, keep_self, n, L, max_dist,
-                    sd.as<unsigned long long>(), sc.as<uint32_t>(), sn.as<int32_t>(), last, oi.as<int64_t>(),
-                    od.as<double>(), oc.as<int32_t>());
-            GD_HIP(hipGetLastError());
-            if (timed) {
-                GD_HIP(hipEventRecord(ev[2], st));
-                GD_HIP(hipEventSynchronize(ev[2]));
-                float m = 0, sl = 0;
-                GD_HIP(hipEventElapsedTime(&m, ev[0], ev[1]));
-                GD_HIP(hipEventElapsedTime(&sl, ev[1], ev[2]));
-                matrix_ms += m;
-                select_ms += sl;
-            }
-        }
-        d2h(idx_out + (b0 - r0) * n, oi.p, (size_t)nb * n * 8, st);
-        d2h(d_out + (b0 - r0) * n, od.p, (size_t)nb * n * 8, st);
-        d2h(count_out + (b0 - r0), oc.p, (size_t)nb * 4, st);
-    }
-    if (timed) {
-        ctx->closest_matrix_ms = matrix_ms;
-        ctx->closest_select_ms = select_ms;
+    if (src.timed) {
+        ctx->closest_matrix_ms = src.fill_ms;
+        ctx->closest_select_ms = src.consume_ms;
     }
 }
 

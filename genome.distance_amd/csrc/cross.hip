@@ -171,99 +171,67 @@ __global__ __launch_bounds__(256) void cross_epilogue_kernel(const int64_t* __re
     }
 }
 
-// The walk every entry point shares: row blocks x ascending column chunks. Per
-// row block the queries' segment rows; per step the plan, the zeroed counts
-// and the join. `after(b0, nb, k0, nk, last)` queues the kernels that consume
-// the step's counts (blk: [nb][nk] int32, inside the timed span), then
-// `out(b0, nb, k0, nk, last)` downloads what the step finished.
-struct CrossWalk {
+// The walk's source (gdist_internal.hpp) for two collections. Per row block
+// the queries' segment rows; per step the plan, the zeroed counts and the join.
+// No cell is left out as self or as lower triangle: row and column index
+// different collections and their comparison decides nothing.
+struct CrossSource : WalkSource {
     gdist_ctx* ctx;
     const gdist_sets* q;
     const gdist_sets* s;
-    int64_t R, W;
-    DevBuf blk, qseg, dunits;
+    DevBuf qseg, dunits;
     std::vector<CrossUnit> units;
-    bool timed;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    double join_ms = 0, select_ms = 0;
     int64_t nunits = 0;
 
-    CrossWalk(gdist_ctx* c, const gdist_sets* queries, const gdist_sets* subjects, int64_t rows, int64_t cols)
-        : ctx(c), q(queries), s(subjects), R(rows), W(cols), timed(c->option(OPT_TIME_KERNELS, 0) != 0) {
-        hipStream_t st = ctx->stream;
-        blk.alloc((size_t)R * W * 4 + 8, st);
-        qseg.alloc((size_t)R * (s->nseg + 1) * 8 + 8, st);
-        if (timed) for (auto& e : ev) GD_HIP(hipEventCreate(&e));
-    }
-    ~CrossWalk() { for (auto& e : ev) if (e) (void)hipEventDestroy(e); }
-
-    template <class After, class Out>
-    void run(int64_t q0, int64_t q1, int64_t c0, int64_t c1, After&& after, Out&& out) {
-        hipStream_t st = ctx->stream;
-        const int nseg = s->nseg;
-        for (int64_t b0 = q0; b0 < q1; b0 += R) {
-            const int64_t b1 = std::min(q1, b0 + R), nb = b1 - b0;
-            segment_rows(ctx, q->codes.as<uint64_t>(), q->off.as<int64_t>() + b0, nb, s->seg_split.as<uint64_t>(), nseg,
-                         qseg.as<int64_t>());
-            for (int64_t k0 = c0; k0 < c1; k0 += W) {
-                const int64_t k1 = std::min(c1, k0 + W), nk = k1 - k0;
-                units.clear();
-                const int64_t budget =
-                    cross_budget(cross_region_codes(q->h_off.data(), b0, b1, s->h_off.data(), k0, k1), ctx->cus);
-                cross_plan(q->h_off.data(), b0, b1, s->h_off.data(), k0, k1, nseg, budget, units);
-                const int64_t nu = (int64_t)units.size();
-                if (nu) {
-                    if (dunits.bytes < (size_t)nu * sizeof(CrossUnit)) dunits.alloc((size_t)nu * sizeof(CrossUnit), st);
-                    h2d(dunits.p, units.data(), (size_t)nu * sizeof(CrossUnit), st);
-                }
-                GD_HIP(hipMemsetAsync(blk.p, 0, (size_t)nb * nk * 4, st));
-                if (timed) GD_HIP(hipEventRecord(ev[0], st));
-                if (nu) {
-                    // two workgroups a CU hold their tables in its LDS; a multiple of the 8 XCDs
-                    const unsigned grid = (unsigned)std::min<int64_t>(nu, (int64_t)std::max(ctx->cus, 8) / 8 * 8 * 2);
-                    cross_join_kernel<<<grid, NTX, 0, st>>>(q->codes.as<uint64_t>(), qseg.as<int64_t>(),
-                                                            s->codes.as<uint64_t>(), s->segoff.as<int64_t>(), nseg,
-                                                            dunits.as<int4>(), nu, nb, k0, k1, blk.as<int32_t>(), nk);
-                    GD_HIP(hipGetLastError());
-                }
-                if (timed) GD_HIP(hipEventRecord(ev[1], st));
-                after(b0, nb, k0, nk, k1 == c1 ? 1 : 0);
-                if (timed) {
-                    GD_HIP(hipEventRecord(ev[2], st));
-                    GD_HIP(hipEventSynchronize(ev[2]));
-                    float j = 0, sl = 0;
-                    GD_HIP(hipEventElapsedTime(&j, ev[0], ev[1]));
-                    GD_HIP(hipEventElapsedTime(&sl, ev[1], ev[2]));
-                    join_ms += j;
-                    select_ms += sl;
-                }
-                out(b0, nb, k0, nk, k1 == c1 ? 1 : 0);
-                nunits += nu;
-            }
-        }
+    CrossSource(gdist_ctx* c, const gdist_sets* queries, const gdist_sets* subjects, unsigned flags)
+        : ctx(c), q(queries), s(subjects) {
+        empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
+        roff = q->off.as<int64_t>();
+        coff = s->off.as<int64_t>();
+        nrsets = q->nsets;
+        ncsets = s->nsets;
+        timed = ctx->option(OPT_TIME_KERNELS, 0) != 0;
     }
 
-    // a consumer kernel that can only be queued from `out` (it needs what the
-    // step downloaded): its time joins select_ms
-    template <class F>
-    void timed_select(F&& f) {
-        hipStream_t st = ctx->stream;
-        if (timed) GD_HIP(hipEventRecord(ev[1], st));
-        f();
-        if (timed) {
-            GD_HIP(hipEventRecord(ev[2], st));
-            GD_HIP(hipEventSynchronize(ev[2]));
-            float sl = 0;
-            GD_HIP(hipEventElapsedTime(&sl, ev[1], ev[2]));
-            select_ms += sl;
-        }
+    void rows(int64_t b0, int64_t b1) override {
+        // the first block is the largest: one allocation a call
+        const size_t need = (size_t)(b1 - b0) * (s->nseg + 1) * 8 + 8;
+        if (qseg.bytes < need) qseg.alloc(need, ctx->stream);
+        segment_rows(ctx, q->codes.as<uint64_t>(), q->off.as<int64_t>() + b0, b1 - b0, s->seg_split.as<uint64_t>(),
+                     s->nseg, qseg.as<int64_t>());
     }
 
-    void report() {
+    void stage(int64_t b0, int64_t b1, int64_t k0, int64_t k1, void* blk) override {
+        hipStream_t st = ctx->stream;
+        units.clear();
+        const int64_t budget =
+            cross_budget(cross_region_codes(q->h_off.data(), b0, b1, s->h_off.data(), k0, k1), ctx->cus);
+        cross_plan(q->h_off.data(), b0, b1, s->h_off.data(), k0, k1, s->nseg, budget, units);
+        const size_t bytes = units.size() * sizeof(CrossUnit);
+        if (dunits.bytes < bytes) dunits.alloc(bytes, st);
+        h2d(dunits.p, units.data(), bytes, st);
+        GD_HIP(hipMemsetAsync(blk, 0, (size_t)(b1 - b0) * (k1 - k0) * 4, st));
+        nunits += (int64_t)units.size();
+    }
+
+    void fill(int64_t b0, int64_t b1, int64_t k0, int64_t k1, void* blk) override {
+        const int64_t nu = (int64_t)units.size();
+        if (!nu) return;
+        // two workgroups a CU hold their tables in its LDS; a multiple of the 8 XCDs
+        const unsigned grid = (unsigned)std::min<int64_t>(nu, (int64_t)std::max(ctx->cus, 8) / 8 * 8 * 2);
+        cross_join_kernel<<<grid, NTX, 0, ctx->stream>>>(q->codes.as<uint64_t>(), qseg.as<int64_t>(),
+                                                         s->codes.as<uint64_t>(), s->segoff.as<int64_t>(), s->nseg,
+                                                         dunits.as<int4>(), nu, b1 - b0, k0, k1,
+                                                         static_cast<int32_t*>(blk), k1 - k0);
+        GD_HIP(hipGetLastError());
+    }
+
+    // gdist_ctx_cross_info, after a walk
+    void report() const {
         ctx->cross_units = nunits;
         if (timed) {
-            ctx->cross_join_ms = join_ms;
-            ctx->cross_select_ms = select_ms;
+            ctx->cross_join_ms = fill_ms;
+            ctx->cross_select_ms = consume_ms;
         }
     }
 };
@@ -277,167 +245,71 @@ static_assert(sizeof(CrossUnit) == sizeof(int4), "units are uploaded as 16-byte 
 void cross_matrix(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
                   int64_t c1, unsigned flags, int32_t* I_out, double* D_out, int64_t ld) {
     hipStream_t st = ctx->stream;
-    const int empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
+    CrossSource src(ctx, q, s, flags);
     int64_t R, W;
     closest_blocks(ctx, q1 - q0, c1 - c0, 12, &R, &W);   // a step's I and D
-    CrossWalk walk(ctx, q, s, R, W);
+    Walk walk(ctx, src, R, W);
     DevBuf dD;
     if (D_out) dD.alloc((size_t)R * W * 8 + 8, st);
     std::vector<int32_t> hI;
     std::vector<double> hD;
-    walk.run(q0, q1, c0, c1, [&](int64_t b0, int64_t nb, int64_t k0, int64_t nk, int) {
+    walk.run(q0, q1, c0, c1, false, [&](const WalkStep& t) {
         if (!D_out) return;
-        const size_t cells = (size_t)nb * nk;
-        const unsigned grid = (unsigned)std::min<int64_t>(ceil_div((int64_t)cells, 256), (int64_t)ctx->cus * 16);
-        cross_epilogue_kernel<<<grid, 256, 0, st>>>(q->off.as<int64_t>(), s->off.as<int64_t>(), b0, nb, k0, nk, empty_nan,
+        const int64_t cells = t.nb * t.nk;
+        const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(cells, 256), (int64_t)ctx->cus * 16);
+        cross_epilogue_kernel<<<grid, 256, 0, st>>>(src.roff, src.coff, t.b0, t.nb, t.k0, t.nk, src.empty_nan,
                                                     walk.blk.as<int32_t>(), dD.as<double>());
         GD_HIP(hipGetLastError());
-    }, [&](int64_t b0, int64_t nb, int64_t k0, int64_t nk, int) {
-        const size_t cells = (size_t)nb * nk;
+    }, [&](const WalkStep& t) {
+        const size_t cells = (size_t)t.nb * t.nk;
         if (D_out) {
             hD.resize(cells);
             d2h(hD.data(), dD.p, cells * 8, st);
-            for (int64_t a = 0; a < nb; a++)
-                std::memcpy(D_out + (b0 - q0 + a) * ld + (k0 - c0), hD.data() + (size_t)a * nk, (size_t)nk * 8);
+            for (int64_t a = 0; a < t.nb; a++)
+                std::memcpy(D_out + (t.b0 - q0 + a) * ld + (t.k0 - c0), hD.data() + (size_t)a * t.nk, (size_t)t.nk * 8);
         }
         if (I_out) {
             hI.resize(cells);
             d2h(hI.data(), walk.blk.p, cells * 4, st);
-            for (int64_t a = 0; a < nb; a++)
-                std::memcpy(I_out + (b0 - q0 + a) * ld + (k0 - c0), hI.data() + (size_t)a * nk, (size_t)nk * 4);
+            for (int64_t a = 0; a < t.nb; a++)
+                std::memcpy(I_out + (t.b0 - q0 + a) * ld + (t.k0 - c0), hI.data() + (size_t)a * t.nk, (size_t)t.nk * 4);
         }
     });
-    walk.report();
+    src.report();
 }
 
-// as cross_matrix; n >= 1, a non-empty rectangle. The counts stay on the
-// device and D is never written: the select folds each step's counts into the
-// rows' lists (closest.hip)
+// The twins: the one-collection call's consumer over a CrossSource. closest
+// and within: a non-empty rectangle (n >= 1); group_stats and histogram: any
 void cross_closest(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
                    int64_t c1, unsigned flags, int n, double max_dist, int64_t* idx_out, double* d_out,
                    int32_t* count_out) {
-    hipStream_t st = ctx->stream;
-    const int empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
-    int L = 128;
-    while (L < n) L <<= 1;
-    int64_t R, W;
-    closest_blocks(ctx, q1 - q0, c1 - c0, 4, &R, &W);
-    CrossWalk walk(ctx, q, s, R, W);
-    DevBuf sd((size_t)R * L * 8 + 8, st), sc((size_t)R * L * 4 + 4, st), sn((size_t)R * 4 + 4, st);
-    DevBuf oi((size_t)R * n * 8 + 8, st), od((size_t)R * n * 8 + 8, st), oc((size_t)R * 4 + 4, st);
-    walk.run(q0, q1, c0, c1, [&](int64_t b0, int64_t nb, int64_t k0, int64_t nk, int last) {
-        if (k0 == c0) GD_HIP(hipMemsetAsync(sn.p, 0, (size_t)nb * 4, st));
-        closest_select_counts(ctx, walk.blk.as<int32_t>(), nk, q->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan, b0,
-                              nb, k0, nk, n, L, max_dist, sd.as<unsigned long long>(), sc.as<uint32_t>(),
-                              sn.as<int32_t>(), last, oi.as<int64_t>(), od.as<double>(), oc.as<int32_t>());
-    }, [&](int64_t b0, int64_t nb, int64_t, int64_t, int last) {
-        if (last) {
-            d2h(idx_out + (b0 - q0) * n, oi.p, (size_t)nb * n * 8, st);
-            d2h(d_out + (b0 - q0) * n, od.p, (size_t)nb * n * 8, st);
-            d2h(count_out + (b0 - q0), oc.p, (size_t)nb * 4, st);
-        }
-    });
-    walk.report();
+    CrossSource src(ctx, q, s, flags);
+    closest_select(ctx, src, q0, q1, c0, c1, n, max_dist, idx_out, d_out, count_out);
+    src.report();
 }
 
-// as cross_matrix; a non-empty rectangle. A row needs its full column width
-// before it can be compacted in (row, column) order: the walk is by row blocks
-// of within()'s sizing over all of [c0, c1), one step a block, and the steps
-// arrive in row order
 void cross_within(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
                   int64_t c1, unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr, int64_t* col_out,
                   double* d_out) {
-    hipStream_t st = ctx->stream;
-    const int empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
-    const int64_t nc = c1 - c0;
-    const int64_t R = within_rows(ctx, q1 - q0, nc, 4);
-    CrossWalk walk(ctx, q, s, R, nc);
-    const int64_t max_tiles = within_tiles(R, nc);
-    DevBuf tcount((size_t)(max_tiles + 1) * 4, st), tbase((size_t)(max_tiles + 1) * 8, st);
-    DevBuf rbase((size_t)(R + 1) * 8, st), scan_tmp;
-    std::vector<int64_t> hbase((size_t)R + 1);
-    int64_t total = 0;   // pairs of the rows before this step
-    rowptr[0] = 0;
-    walk.run(q0, q1, c0, c1, [&](int64_t b0, int64_t nb, int64_t k0, int64_t nk, int) {
-        within_count_counts(ctx, walk.blk.as<int32_t>(), nk, q->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan, b0,
-                            nb, k0, nk, max_dist, tcount.as<int32_t>(), tbase.as<int64_t>(), rbase.as<int64_t>(),
-                            scan_tmp);
-    }, [&](int64_t b0, int64_t nb, int64_t k0, int64_t nk, int) {
-        d2h(hbase.data(), rbase.p, (size_t)(nb + 1) * 8, st);
-        int64_t* rp = rowptr + (b0 - q0);
-        for (int64_t a = 0; a <= nb; a++) rp[a] = total + hbase[a];
-        const int64_t step = hbase[nb];
-        const int64_t fit = std::min(step, std::max<int64_t>(capacity - total, 0));
-        if (fit > 0) {
-            DevBuf sc((size_t)fit * 8, st), sd((size_t)fit * 8, st);
-            walk.timed_select([&] {
-                within_write_counts(ctx, walk.blk.as<int32_t>(), nk, q->off.as<int64_t>(), s->off.as<int64_t>(),
-                                    empty_nan, b0, nb, k0, nk, max_dist, tbase.as<int64_t>(), fit, sc.as<int64_t>(),
-                                    sd.as<double>());
-            });
-            d2h(col_out + total, sc.p, (size_t)fit * 8, st);
-            d2h(d_out + total, sd.p, (size_t)fit * 8, st);
-        }
-        total += step;
-    });
-    walk.report();
+    CrossSource src(ctx, q, s, flags);
+    within_compact(ctx, src, q0, q1, c0, c1, max_dist, capacity, rowptr, col_out, d_out);
+    src.report();
 }
 
-// as cross_matrix, any rectangle (an empty one: the n == 0 form). Each step's
-// counts are folded into the call's accumulators, as group_stats() folds them
 void cross_group_stats(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
                        int64_t c1, unsigned flags, int ntypes, const int32_t* qlabels, const int32_t* slabels,
                        gdist_group_side* out, int64_t* bad) {
-    hipStream_t st = ctx->stream;
-    const int empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
-    const size_t nslots = group_slots(ntypes);
-    std::vector<unsigned long long> h(nslots, 0ull);
-    if (q1 > q0 && c1 > c0) {
-        int64_t R, W;
-        closest_blocks(ctx, q1 - q0, c1 - c0, 4, &R, &W);
-        CrossWalk walk(ctx, q, s, R, W);
-        DevBuf qlab((size_t)ntypes * q->nsets * 4, st), slab((size_t)ntypes * s->nsets * 4, st), acc(nslots * 8, st);
-        h2d(qlab.p, qlabels, (size_t)ntypes * q->nsets * 4, st);
-        h2d(slab.p, slabels, (size_t)ntypes * s->nsets * 4, st);
-        GD_HIP(hipMemsetAsync(acc.p, 0, nslots * 8, st));
-        walk.run(q0, q1, c0, c1, [&](int64_t b0, int64_t nb, int64_t k0, int64_t nk, int) {
-            group_reduce_counts(ctx, walk.blk.as<int32_t>(), nk, q->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan,
-                                b0, nb, k0, nk, ntypes, qlab.as<int32_t>(), q->nsets, slab.as<int32_t>(), s->nsets,
-                                acc.as<unsigned long long>());
-        }, [](int64_t, int64_t, int64_t, int64_t, int) {});
-        d2h(h.data(), acc.p, nslots * 8, st);
-        walk.report();
-    }
-    group_finish(h.data(), ntypes, out, bad);
+    CrossSource src(ctx, q, s, flags);
+    group_reduce(ctx, src, q0, q1, c0, c1, ntypes, qlabels, slabels, out, bad);
+    if (q1 > q0 && c1 > c0) src.report();
 }
 
-// as cross_group_stats with the bucket counts of histogram()
 void cross_histogram(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
                      int64_t c1, unsigned flags, int nedges, const double* edges, int ntypes, const int32_t* qlabels,
                      const int32_t* slabels, int64_t* counts, int64_t* nans, int64_t* bad) {
-    hipStream_t st = ctx->stream;
-    const int empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
-    const size_t nslots = hist_slots(nedges, ntypes);
-    std::vector<unsigned long long> h(nslots, 0ull);
-    if (q1 > q0 && c1 > c0) {
-        int64_t R, W;
-        closest_blocks(ctx, q1 - q0, c1 - c0, 4, &R, &W);
-        CrossWalk walk(ctx, q, s, R, W);
-        DevBuf qlab((size_t)ntypes * q->nsets * 4, st), slab((size_t)ntypes * s->nsets * 4, st);
-        DevBuf edg((size_t)nedges * 8, st), acc(nslots * 8, st);
-        h2d(qlab.p, qlabels, (size_t)ntypes * q->nsets * 4, st);
-        h2d(slab.p, slabels, (size_t)ntypes * s->nsets * 4, st);
-        h2d(edg.p, edges, (size_t)nedges * 8, st);
-        GD_HIP(hipMemsetAsync(acc.p, 0, nslots * 8, st));
-        walk.run(q0, q1, c0, c1, [&](int64_t b0, int64_t nb, int64_t k0, int64_t nk, int) {
-            hist_counts(ctx, walk.blk.as<int32_t>(), nk, q->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan, b0, nb,
-                        k0, nk, ntypes, qlab.as<int32_t>(), q->nsets, slab.as<int32_t>(), s->nsets, edg.as<double>(),
-                        nedges, acc.as<unsigned long long>());
-        }, [](int64_t, int64_t, int64_t, int64_t, int) {});
-        d2h(h.data(), acc.p, nslots * 8, st);
-        walk.report();
-    }
-    hist_finish(h.data(), nedges, ntypes, counts, nans, bad);
+    CrossSource src(ctx, q, s, flags);
+    hist_count(ctx, src, q0, q1, c0, c1, nedges, edges, ntypes, qlabels, slabels, counts, nans, bad);
+    if (q1 > q0 && c1 > c0) src.report();
 }
 
 }  // namespace gdist

@@ -1404,43 +1404,98 @@ int gdist_lsh_closest(gdist_ctx* ctx, const gdist_lsh* lsh, const gdist_sets* qu
 }
 
 // ---------------------------------------------------------------------------
+// What the table-free queries (gdist_closest, _group_stats, _within, _histogram
+// and gdist_cross_*) check and set up alike.
+// a rectangle of a collection of this context
+static void check_rect(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, int64_t r1, int64_t c0, int64_t c1) {
+    check_sets(sets);
+    GD_REQUIRE(sets->ctx == ctx, "sets belong to another context");
+    GD_REQUIRE(0 <= r0 && r0 <= r1 && r1 <= sets->nsets && 0 <= c0 && c0 <= c1 && c1 <= sets->nsets,
+               "row/column range outside the set collection");
+}
+
+// sketches need their signatures, kmer sets a method the collection can run
+static void check_method(const gdist_sets* sets, int method) {
+    if (sets->kind == GDIST_SKETCH) return check_codes(sets);
+    GD_REQUIRE(method >= GDIST_METHOD_AUTO && method <= GDIST_METHOD_BITSET, "unknown method");
+    GD_REQUIRE(method != GDIST_METHOD_SORTED || sets->has_codes, "this collection holds bitsets only");
+}
+
+static void check_column_keys(const gdist_sets* sets) {
+    GD_REQUIRE(sets->nsets < (int64_t)UINT32_MAX, "too many sets for 32-bit column keys");
+}
+
+static void check_edges(int nedges, const double* edges) {
+    for (int e = 0; e < nedges; e++) {
+        GD_REQUIRE(edges[e] == edges[e], "an edge is NaN");
+        // -0.0 == 0.0: a signed-zero pair is not ascending either
+        GD_REQUIRE(e == 0 || edges[e - 1] < edges[e], "edges are not strictly ascending");
+    }
+}
+
+// the method a non-empty rectangle of kmer sets runs; sketches have none
+static int rect_method(gdist_ctx* ctx, gdist_sets* s, int method, int64_t nr, int64_t nc) {
+    if (s->kind == GDIST_SKETCH || nr == 0 || nc == 0) return GDIST_METHOD_AUTO;
+    return resolve_method(ctx, s, method, (double)nr * (double)nc);
+}
+
+// the closest answer of nr > 0 rows with no neighbour to list (n == 0 or no columns)
+static void closest_none(int64_t nr, int n, int64_t* idx_out, double* d_out, int32_t* count_out) {
+    std::fill(count_out, count_out + nr, 0);
+    if (n) {
+        std::fill(idx_out, idx_out + nr * n, (int64_t)-1);
+        std::fill(d_out, d_out + nr * n, 1.0);
+    }
+}
+
+static void begin_call(gdist_ctx* ctx) {
+    ctx->pending = false;          // an unread previous call's times are dropped, not waited for
+    ctx->last = Timing{};
+}
+
+// what every gdist_cross_* call refuses alike, before any work
+static void check_cross(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects, int64_t q0, int64_t q1,
+                        int64_t c0, int64_t c1, unsigned flags) {
+    check_sets(queries);
+    check_sets(subjects);
+    GD_REQUIRE(queries->ctx == ctx && subjects->ctx == ctx, "sets belong to another context");
+    GD_REQUIRE(queries->kind != GDIST_SKETCH && subjects->kind != GDIST_SKETCH,
+               "cross calls run on kmer sets (sketches: gdist_lsh_closest)");
+    check_same_spec(queries, subjects);
+    check_codes(queries);
+    check_codes(subjects);
+    GD_REQUIRE(0 <= q0 && q0 <= q1 && q1 <= queries->nsets, "query range outside the query collection");
+    GD_REQUIRE(0 <= c0 && c0 <= c1 && c1 <= subjects->nsets, "column range outside the subject collection");
+    GD_REQUIRE(!(flags & ~GDIST_EMPTY_NAN), "cross calls take no flag but GDIST_EMPTY_NAN");
+    GD_REQUIRE(subjects->nsets < (int64_t)UINT32_MAX, "too many subjects for 32-bit column keys");
+}
+
+static void begin_cross(gdist_ctx* ctx) {
+    ctx->cross_join_ms = ctx->cross_select_ms = -1.0;
+    ctx->cross_units = 0;
+    begin_call(ctx);
+}
+
 int gdist_closest(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
                   unsigned flags, int n, double max_dist, int64_t* idx_out, double* d_out, int32_t* count_out) {
     return guard([&] {
         use_device(ctx);
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        check_sets(sets);
-        GD_REQUIRE(sets->ctx == ctx, "sets belong to another context");
-        GD_REQUIRE(0 <= r0 && r0 <= r1 && r1 <= sets->nsets && 0 <= c0 && c0 <= c1 && c1 <= sets->nsets,
-                   "row/column range outside the set collection");
+        check_rect(ctx, sets, r0, r1, c0, c1);
         GD_REQUIRE(n >= 0 && n <= GDIST_CLOSEST_MAX_N, "n outside 0 .. GDIST_CLOSEST_MAX_N");
         GD_REQUIRE(max_dist == max_dist, "max_dist is NaN");
         GD_REQUIRE(!(flags & (GDIST_UPPER_TRIANGLE | GDIST_OUT_DEVICE)),
                    "gdist_closest supports neither GDIST_UPPER_TRIANGLE nor GDIST_OUT_DEVICE");
-        const bool sketch = sets->kind == GDIST_SKETCH;
-        if (sketch) {
-            check_codes(sets);
-        } else {
-            GD_REQUIRE(method >= GDIST_METHOD_AUTO && method <= GDIST_METHOD_BITSET, "unknown method");
-            GD_REQUIRE(method != GDIST_METHOD_SORTED || sets->has_codes, "this collection holds bitsets only");
-        }
-        GD_REQUIRE(sets->nsets < (int64_t)UINT32_MAX, "too many sets for 32-bit column keys");
+        check_method(sets, method);
+        check_column_keys(sets);
         const int64_t nr = r1 - r0, nc = c1 - c0;
         GD_REQUIRE(nr == 0 || (count_out && (n == 0 || (idx_out && d_out))), "null output");
         ctx->closest_matrix_ms = ctx->closest_select_ms = -1.0;
         if (nr == 0) return;
-        if (n == 0 || nc == 0) {
-            std::fill(count_out, count_out + nr, 0);
-            if (n) {
-                std::fill(idx_out, idx_out + nr * n, (int64_t)-1);
-                std::fill(d_out, d_out + nr * n, 1.0);
-            }
-            return;
-        }
+        if (n == 0 || nc == 0) return closest_none(nr, n, idx_out, d_out, count_out);
         auto* s = const_cast<gdist_sets*>(sets);
-        const int m = sketch ? GDIST_METHOD_AUTO : resolve_method(ctx, s, method, (double)nr * (double)nc);
-        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
-        ctx->last = Timing{};
+        const int m = rect_method(ctx, s, method, nr, nc);
+        begin_call(ctx);
         gdist::closest(ctx, s, r0, r1, c0, c1, m, flags, n, max_dist, idx_out, d_out, count_out);
     });
 }
@@ -1461,26 +1516,15 @@ int gdist_group_stats(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, int64_
     return guard([&] {
         use_device(ctx);
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        check_sets(sets);
-        GD_REQUIRE(sets->ctx == ctx, "sets belong to another context");
-        GD_REQUIRE(0 <= r0 && r0 <= r1 && r1 <= sets->nsets && 0 <= c0 && c0 <= c1 && c1 <= sets->nsets,
-                   "row/column range outside the set collection");
+        check_rect(ctx, sets, r0, r1, c0, c1);
         GD_REQUIRE(ntypes >= 1 && ntypes <= GDIST_GROUP_MAX_TYPES, "ntypes outside 1 .. GDIST_GROUP_MAX_TYPES");
         GD_REQUIRE(labels && out && bad, "null labels or output");
         GD_REQUIRE(!(flags & GDIST_OUT_DEVICE), "gdist_group_stats does not support GDIST_OUT_DEVICE");
-        const bool sketch = sets->kind == GDIST_SKETCH;
-        if (sketch) {
-            check_codes(sets);
-        } else {
-            GD_REQUIRE(method >= GDIST_METHOD_AUTO && method <= GDIST_METHOD_BITSET, "unknown method");
-            GD_REQUIRE(method != GDIST_METHOD_SORTED || sets->has_codes, "this collection holds bitsets only");
-        }
+        check_method(sets, method);
         const int64_t nr = r1 - r0, nc = c1 - c0;
         auto* s = const_cast<gdist_sets*>(sets);
-        int m = GDIST_METHOD_AUTO;
-        if (!sketch && nr > 0 && nc > 0) m = resolve_method(ctx, s, method, (double)nr * (double)nc);
-        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
-        ctx->last = Timing{};
+        const int m = rect_method(ctx, s, method, nr, nc);
+        begin_call(ctx);
         // into locals first: a failure on the device leaves the outputs untouched too
         std::vector<gdist_group_side> o((size_t)2 * ntypes);
         std::vector<int64_t> b((size_t)ntypes);
@@ -1516,29 +1560,18 @@ int gdist_within(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, int64_t r1,
     return guard([&] {
         use_device(ctx);
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        check_sets(sets);
-        GD_REQUIRE(sets->ctx == ctx, "sets belong to another context");
-        GD_REQUIRE(0 <= r0 && r0 <= r1 && r1 <= sets->nsets && 0 <= c0 && c0 <= c1 && c1 <= sets->nsets,
-                   "row/column range outside the set collection");
+        check_rect(ctx, sets, r0, r1, c0, c1);
         GD_REQUIRE(max_dist == max_dist, "max_dist is NaN");
         GD_REQUIRE(capacity >= 0, "negative capacity");
         GD_REQUIRE(rowptr_out && total, "null rowptr_out or total");
         GD_REQUIRE(capacity == 0 || (col_out && d_out), "null col_out or d_out with capacity > 0");
         GD_REQUIRE(!(flags & GDIST_OUT_DEVICE), "gdist_within does not support GDIST_OUT_DEVICE");
-        const bool sketch = sets->kind == GDIST_SKETCH;
-        if (sketch) {
-            check_codes(sets);
-        } else {
-            GD_REQUIRE(method >= GDIST_METHOD_AUTO && method <= GDIST_METHOD_BITSET, "unknown method");
-            GD_REQUIRE(method != GDIST_METHOD_SORTED || sets->has_codes, "this collection holds bitsets only");
-        }
-        GD_REQUIRE(sets->nsets < (int64_t)UINT32_MAX, "too many sets for 32-bit column keys");
+        check_method(sets, method);
+        check_column_keys(sets);
         const int64_t nr = r1 - r0, nc = c1 - c0;
         auto* s = const_cast<gdist_sets*>(sets);
-        int m = GDIST_METHOD_AUTO;
-        if (!sketch && nr > 0 && nc > 0) m = resolve_method(ctx, s, method, (double)nr * (double)nc);
-        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
-        ctx->last = Timing{};
+        const int m = rect_method(ctx, s, method, nr, nc);
+        begin_call(ctx);
         // the row pointers into a local first: a failure on the device leaves them and *total untouched
         std::vector<int64_t> rp((size_t)nr + 1, 0);
         gdist::within(ctx, s, r0, r1, c0, c1, m, flags, max_dist, capacity, rp.data(), col_out, d_out);
@@ -1597,30 +1630,6 @@ int gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, int
 }
 
 // ---------------------------------------------------------------------------
-// what every gdist_cross_* call refuses alike, before any work
-static void check_cross(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects, int64_t q0, int64_t q1,
-                        int64_t c0, int64_t c1, unsigned flags) {
-    check_sets(queries);
-    check_sets(subjects);
-    GD_REQUIRE(queries->ctx == ctx && subjects->ctx == ctx, "sets belong to another context");
-    GD_REQUIRE(queries->kind != GDIST_SKETCH && subjects->kind != GDIST_SKETCH,
-               "cross calls run on kmer sets (sketches: gdist_lsh_closest)");
-    check_same_spec(queries, subjects);
-    check_codes(queries);
-    check_codes(subjects);
-    GD_REQUIRE(0 <= q0 && q0 <= q1 && q1 <= queries->nsets, "query range outside the query collection");
-    GD_REQUIRE(0 <= c0 && c0 <= c1 && c1 <= subjects->nsets, "column range outside the subject collection");
-    GD_REQUIRE(!(flags & ~GDIST_EMPTY_NAN), "cross calls take no flag but GDIST_EMPTY_NAN");
-    GD_REQUIRE(subjects->nsets < (int64_t)UINT32_MAX, "too many subjects for 32-bit column keys");
-}
-
-static void begin_cross(gdist_ctx* ctx) {
-    ctx->cross_join_ms = ctx->cross_select_ms = -1.0;
-    ctx->cross_units = 0;
-    ctx->pending = false;          // an unread previous call's times are dropped, not waited for
-    ctx->last = Timing{};
-}
-
 int gdist_cross_matrix(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects, int64_t q0, int64_t q1,
                        int64_t c0, int64_t c1, unsigned flags, int32_t* I_out, double* D_out, int64_t ld) {
     return guard([&] {
@@ -1653,14 +1662,7 @@ int gdist_cross_closest(gdist_ctx* ctx, const gdist_sets* queries, const gdist_s
         auto* s = const_cast<gdist_sets*>(subjects);
         begin_cross(ctx);
         if (nr == 0) return;
-        if (n == 0 || nc == 0) {
-            std::fill(count_out, count_out + nr, 0);
-            if (n) {
-                std::fill(idx_out, idx_out + nr * n, (int64_t)-1);
-                std::fill(d_out, d_out + nr * n, 1.0);
-            }
-            return;
-        }
+        if (n == 0 || nc == 0) return closest_none(nr, n, idx_out, d_out, count_out);
         if (!s->segoff.p) build_segments(ctx, s);
         gdist::cross_closest(ctx, queries, s, q0, q1, c0, c1, flags, n, max_dist, idx_out, d_out, count_out);
     });
@@ -1724,11 +1726,7 @@ int gdist_cross_histogram(gdist_ctx* ctx, const gdist_sets* queries, const gdist
         GD_REQUIRE(ntypes >= 0 && ntypes <= GDIST_GROUP_MAX_TYPES, "ntypes outside 0 .. GDIST_GROUP_MAX_TYPES");
         GD_REQUIRE(edges && counts_out && nans_out, "null edges or output");
         GD_REQUIRE(ntypes == 0 || (qlabels && slabels && bad_out), "null labels or bad_out with ntypes > 0");
-        for (int e = 0; e < nedges; e++) {
-            GD_REQUIRE(edges[e] == edges[e], "an edge is NaN");
-            // -0.0 == 0.0: a signed-zero pair is not ascending either
-            GD_REQUIRE(e == 0 || edges[e - 1] < edges[e], "edges are not strictly ascending");
-        }
+        check_edges(nedges, edges);
         auto* s = const_cast<gdist_sets*>(subjects);
         begin_cross(ctx);
         if (q1 > q0 && c1 > c0 && !s->segoff.p) build_segments(ctx, s);
@@ -1760,33 +1758,18 @@ int gdist_histogram(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, int64_t 
     return guard([&] {
         use_device(ctx);
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        check_sets(sets);
-        GD_REQUIRE(sets->ctx == ctx, "sets belong to another context");
-        GD_REQUIRE(0 <= r0 && r0 <= r1 && r1 <= sets->nsets && 0 <= c0 && c0 <= c1 && c1 <= sets->nsets,
-                   "row/column range outside the set collection");
+        check_rect(ctx, sets, r0, r1, c0, c1);
         GD_REQUIRE(nedges >= 1 && nedges <= GDIST_HIST_MAX_EDGES, "nedges outside 1 .. GDIST_HIST_MAX_EDGES");
         GD_REQUIRE(ntypes >= 0 && ntypes <= GDIST_GROUP_MAX_TYPES, "ntypes outside 0 .. GDIST_GROUP_MAX_TYPES");
         GD_REQUIRE(edges && counts_out && nans_out, "null edges or output");
         GD_REQUIRE(ntypes == 0 || (labels && bad_out), "null labels or bad_out with ntypes > 0");
         GD_REQUIRE(!(flags & GDIST_OUT_DEVICE), "gdist_histogram does not support GDIST_OUT_DEVICE");
-        for (int e = 0; e < nedges; e++) {
-            GD_REQUIRE(edges[e] == edges[e], "an edge is NaN");
-            // -0.0 == 0.0: a signed-zero pair is not ascending either
-            GD_REQUIRE(e == 0 || edges[e - 1] < edges[e], "edges are not strictly ascending");
-        }
-        const bool sketch = sets->kind == GDIST_SKETCH;
-        if (sketch) {
-            check_codes(sets);
-        } else {
-            GD_REQUIRE(method >= GDIST_METHOD_AUTO && method <= GDIST_METHOD_BITSET, "unknown method");
-            GD_REQUIRE(method != GDIST_METHOD_SORTED || sets->has_codes, "this collection holds bitsets only");
-        }
+        check_edges(nedges, edges);
+        check_method(sets, method);
         const int64_t nr = r1 - r0, nc = c1 - c0;
         auto* s = const_cast<gdist_sets*>(sets);
-        int m = GDIST_METHOD_AUTO;
-        if (!sketch && nr > 0 && nc > 0) m = resolve_method(ctx, s, method, (double)nr * (double)nc);
-        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
-        ctx->last = Timing{};
+        const int m = rect_method(ctx, s, method, nr, nc);
+        begin_call(ctx);
         // into locals first: a failure on the device leaves the outputs untouched too
         const size_t series = ntypes ? (size_t)2 * ntypes : 1;
         std::vector<int64_t> cn(series * ((size_t)nedges + 1)), na(series), b((size_t)ntypes);

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <climits>
 #include <functional>
 #include <cstdint>
@@ -723,17 +724,136 @@ void distance_epilogue(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t 
                        int64_t c1, bool upper, unsigned flags, const int32_t* d_I, int64_t ldI,
                        double* d_D, int64_t ldD);
 
+// ---------------------------------------------------------------------------
+// The block walk of the table-free queries (gdist_closest, _within,
+// _group_stats, _histogram and their gdist_cross_* twins, gdist_cross_matrix):
+// row blocks x ascending column chunks. Per step a source fills the block on
+// the device and the family's kernels consume it while it is resident.
+//
+// What fills a step, and what the consumers' kernels need to read it: one
+// collection against itself (SelfSource) or queries against subjects
+// (CrossSource, cross.hip). A twin differs from its one-collection call by
+// nothing but its source.
+struct WalkSource {
+    bool from_counts = true;   // a block holds intersection counts (int32); else distances (double)
+    int keep_self = 1, upper = 0, empty_nan = 0;
+    const int64_t *roff = nullptr, *coff = nullptr;   // the rows' / the columns' set offsets (null: distances)
+    int64_t nrsets = 0, ncsets = 0;                   // the rows' / the columns' label stride
+    bool timed = false;                               // option time_kernels
+    double fill_ms = 0, consume_ms = 0;               // HIP-event time over all steps (timed)
+    virtual ~WalkSource() = default;
+    size_t elem() const { return from_counts ? 4 : 8; }
+    // once a row block, before its steps
+    virtual void rows(int64_t, int64_t) {}
+    // a step's host work and uploads, ahead of the timed span
+    virtual void stage(int64_t, int64_t, int64_t, int64_t, void*) {}
+    // queues the kernels that leave rows [b0, b1) x columns [k0, k1) in blk, row stride k1 - k0
+    virtual void fill(int64_t b0, int64_t b1, int64_t k0, int64_t k1, void* blk) = 0;
+};
+
+// The only place with the sketch / bitset / sorted dispatch (closest.hip).
+// method: SORTED or BITSET, resolved by the caller; ignored for sketches
+struct SelfSource : WalkSource {
+    gdist_ctx* ctx;
+    const gdist_sets* s;
+    int method;
+    unsigned mflags;
+    SelfSource(gdist_ctx* c, const gdist_sets* sets, int method, unsigned flags);
+    void fill(int64_t b0, int64_t b1, int64_t k0, int64_t k1, void* blk) override;
+};
+
+// rows [b0, b0 + nb) x columns [k0, k0 + nk); last: the row block's last chunk
+struct WalkStep {
+    int64_t b0, nb, k0, nk;
+    int last;
+};
+
+struct Walk {
+    gdist_ctx* ctx;
+    WalkSource& src;
+    int64_t R, W;   // rows a block, columns a chunk
+    DevBuf blk;     // the step's block: [nb][nk] of src.elem() bytes
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+
+    Walk(gdist_ctx* c, WalkSource& source, int64_t rows, int64_t cols) : ctx(c), src(source), R(rows), W(cols) {
+        blk.alloc((size_t)R * W * src.elem() + 8, ctx->stream);
+        if (src.timed) for (auto& e : ev) GD_HIP(hipEventCreate(&e));
+    }
+    ~Walk() { for (auto& e : ev) if (e) (void)hipEventDestroy(e); }
+    Walk(const Walk&) = delete;
+    Walk& operator=(const Walk&) = delete;
+
+    // Under src.upper a step wholly on or left of the diagonal is skipped
+    // before any fill; `trim` (gdist_within: W is the full width) also starts
+    // a row block's columns at max(c0, b0 + 1). consume(step) queues the
+    // kernels that read blk, inside the timed span; out(step) then downloads
+    // what the step finished.
+    template <class Consume, class Out>
+    void run(int64_t r0, int64_t r1, int64_t c0, int64_t c1, bool trim, Consume&& consume, Out&& out) {
+        hipStream_t st = ctx->stream;
+        for (int64_t b0 = r0; b0 < r1; b0 += R) {
+            const int64_t b1 = std::min(r1, b0 + R);
+            src.rows(b0, b1);
+            for (int64_t k0 = (trim && src.upper) ? std::max(c0, b0 + 1) : c0; k0 < c1; k0 += W) {
+                const int64_t k1 = std::min(c1, k0 + W);
+                if (src.upper && k1 - 1 <= b0) continue;
+                const WalkStep step{b0, b1 - b0, k0, k1 - k0, k1 == c1 ? 1 : 0};
+                src.stage(b0, b1, k0, k1, blk.p);
+                if (src.timed) GD_HIP(hipEventRecord(ev[0], st));
+                src.fill(b0, b1, k0, k1, blk.p);
+                timed_select([&] { consume(step); });
+                if (src.timed) src.fill_ms += elapsed(0, 1);
+                out(step);
+            }
+        }
+    }
+
+    // f queues consumer kernels; their time joins consume_ms. run() uses it
+    // for consume; a kernel that can only be queued from out (it needs what
+    // the step downloaded) is wrapped in it by the caller
+    template <class F>
+    void timed_select(F&& f) {
+        hipStream_t st = ctx->stream;
+        if (src.timed) GD_HIP(hipEventRecord(ev[1], st));
+        f();
+        if (src.timed) {
+            GD_HIP(hipEventRecord(ev[2], st));
+            GD_HIP(hipEventSynchronize(ev[2]));
+            src.consume_ms += elapsed(1, 2);
+        }
+    }
+
+    double elapsed(int a, int b) {
+        float ms = 0;
+        GD_HIP(hipEventElapsedTime(&ms, ev[a], ev[b]));
+        return ms;
+    }
+};
+
+// The rows' and the columns' labels of group_reduce / hist_count on the device
+// (host: [ntypes][src.nrsets] and [ntypes][src.ncsets]; null with ntypes == 0);
+// one upload when both are the same array
+struct WalkLabels {
+    DevBuf r, c;
+    const int32_t *rows, *cols;
+    WalkLabels(const WalkSource& src, int ntypes, const int32_t* rl, const int32_t* cl, hipStream_t st) {
+        r.alloc((size_t)ntypes * src.nrsets * 4, st);
+        h2d(r.p, rl, r.bytes, st);
+        rows = cols = r.as<int32_t>();
+        if (cl == rl && src.ncsets == src.nrsets) return;
+        c.alloc((size_t)ntypes * src.ncsets * 4, st);
+        h2d(c.p, cl, c.bytes, st);
+        cols = c.as<int32_t>();
+    }
+};
+
 // closest.hip — exact top-n within max_dist per query row (gdist_closest)
 void closest_blocks(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem, int64_t* rows, int64_t* cols);
 void closest(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
              unsigned flags, int n, double max_dist, int64_t* idx_out, double* d_out, int32_t* count_out);
-
-// one select step of closest() over counts whose rows and columns belong to
-// two collections (their offsets d_roff / d_coff); no column is left out as self
-void closest_select_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff,
-                           const int64_t* d_coff, int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc,
-                           int n, int L, double max_dist, unsigned long long* st_d, uint32_t* st_c, int32_t* st_n,
-                           int last, int64_t* d_idx, double* d_d, int32_t* d_count);
+// the walk and the select behind closest() and cross_closest(): a non-empty rectangle, n >= 1
+void closest_select(gdist_ctx* ctx, WalkSource& src, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int n,
+                    double max_dist, int64_t* idx_out, double* d_out, int32_t* count_out);
 
 // cross.hip — query sets against a resident collection (gdist_cross_*)
 // every argument checked by the caller, the subjects' segment index built; host outputs
@@ -759,16 +879,10 @@ void cross_histogram(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, i
 // labels: host, [ntypes][nsets]; out: [ntypes][2], bad: [ntypes], written whole
 void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
                  unsigned flags, int ntypes, const int32_t* labels, gdist_group_side* out, int64_t* bad);
-// one reduce step of group_stats() over counts whose rows and columns belong
-// to two collections (offsets d_roff / d_coff, labels d_rlab [ntypes][nrsets] /
-// d_clab [ntypes][ncsets]); every cell counts. d_acc: group_slots(ntypes)
-// uint64, zeroed by the caller; group_finish turns its host copy into the sides
-size_t group_slots(int ntypes);
-void group_reduce_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
-                         int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, int ntypes,
-                         const int32_t* d_rlab, int64_t nrsets, const int32_t* d_clab, int64_t ncsets,
-                         unsigned long long* d_acc);
-void group_finish(const unsigned long long* h, int ntypes, gdist_group_side* out, int64_t* bad);
+// the walk and the reduce behind group_stats() and cross_group_stats(), any
+// rectangle; rlabels / clabels: host, [ntypes][src.nrsets] / [ntypes][src.ncsets]
+void group_reduce(gdist_ctx* ctx, WalkSource& src, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int ntypes,
+                  const int32_t* rlabels, const int32_t* clabels, gdist_group_side* out, int64_t* bad);
 
 // within.hip — every pair within max_dist as CSR (gdist_within)
 // method: SORTED or BITSET (resolved by the caller); ignored for sketches.
@@ -777,18 +891,9 @@ void group_finish(const unsigned long long* h, int ntypes, gdist_group_side* out
 int64_t within_rows(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem);
 void within(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
             unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr, int64_t* col_out, double* d_out);
-// the compaction of within() over one row block's counts whose rows and
-// columns belong to two collections; every cell may qualify. count: the tile
-// counts (d_tcount: within_tiles + 1 int32), their scan (d_tbase: as many
-// int64) and the rows' bases (d_rbase: nrows + 1). write: the survivors at
-// positions < fit into d_col / d_d
-int64_t within_tiles(int64_t nrows, int64_t nc);
-void within_count_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
-                         int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, double max_dist,
-                         int32_t* d_tcount, int64_t* d_tbase, int64_t* d_rbase, DevBuf& scan_tmp);
-void within_write_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
-                         int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, double max_dist,
-                         const int64_t* d_tbase, int64_t fit, int64_t* d_col, double* d_d);
+// the walk and the compaction behind within() and cross_within(): a non-empty rectangle
+void within_compact(gdist_ctx* ctx, WalkSource& src, int64_t r0, int64_t r1, int64_t c0, int64_t c1, double max_dist,
+                    int64_t capacity, int64_t* rowptr, int64_t* col_out, double* d_out);
 
 // hist.hip — distribution of the distances over bucket edges (gdist_histogram)
 // method: SORTED or BITSET (resolved by the caller, every argument checked);
@@ -798,15 +903,11 @@ void within_write_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const i
 void histogram(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
                unsigned flags, int nedges, const double* edges, int ntypes, const int32_t* labels, int64_t* counts,
                int64_t* nans, int64_t* bad);
-// one counting step of histogram() over counts whose rows and columns belong
-// to two collections (as group_reduce_counts; the labels are not read when
-// ntypes == 0). d_acc: hist_slots(nedges, ntypes) uint64, zeroed by the caller
-size_t hist_slots(int nedges, int ntypes);
-void hist_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
-                 int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, int ntypes,
-                 const int32_t* d_rlab, int64_t nrsets, const int32_t* d_clab, int64_t ncsets, const double* d_edges,
-                 int nedges, unsigned long long* d_acc);
-void hist_finish(const unsigned long long* h, int nedges, int ntypes, int64_t* counts, int64_t* nans, int64_t* bad);
+// the walk and the counting behind histogram() and cross_histogram(), any
+// rectangle; the labels as group_reduce takes them, not read when ntypes == 0
+void hist_count(gdist_ctx* ctx, WalkSource& src, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int nedges,
+                const double* edges, int ntypes, const int32_t* rlabels, const int32_t* clabels, int64_t* counts,
+                int64_t* nans, int64_t* bad);
 
 // pairs.hip — the distances of a pair list (gdist_pairs)
 // method: SORTED or BITSET (resolved by the caller, every argument checked);

@@ -231,22 +231,8 @@ dim3 group_grid(const gdist_ctx* ctx, int64_t nrows, int64_t nc, int ntypes) {
 
 }  // namespace
 
-size_t group_slots(int ntypes) { return (size_t)ntypes * kTypeSlots; }
-
-void group_reduce_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
-                         int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, int ntypes,
-                         const int32_t* d_rlab, int64_t nrsets, const int32_t* d_clab, int64_t ncsets,
-                         unsigned long long* d_acc) {
-    const dim3 grid = group_grid(ctx, nrows, nc, ntypes);
-    const int64_t nseg = ceil_div(nc, kSegCols);
-    group_reduce_kernel<true><<<grid, 256, 0, ctx->stream>>>(d_I, ld, d_roff, d_coff, empty_nan, q0, nrows, c0, nc, 0,
-                                                             d_rlab, nrsets, d_clab, ncsets, nrows * nseg, nseg,
-                                                             d_acc);
-    GD_HIP(hipGetLastError());
-}
-
 // carries of the digit slots, min / max from their patterns, mean and sdev
-void group_finish(const unsigned long long* h, int ntypes, gdist_group_side* out, int64_t* bad) {
+static void group_finish(const unsigned long long* h, int ntypes, gdist_group_side* out, int64_t* bad) {
     for (int t = 0; t < ntypes; t++) {
         const unsigned long long* g = h + (size_t)t * kTypeSlots;
         for (int k = 0; k < 2; k++) {
@@ -273,80 +259,41 @@ void group_finish(const unsigned long long* h, int ntypes, gdist_group_side* out
     }
 }
 
-void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
-                 unsigned flags, int ntypes, const int32_t* labels, gdist_group_side* out, int64_t* bad) {
+// Any order of the steps: the sums do not depend on it.
+void group_reduce(gdist_ctx* ctx, WalkSource& src, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int ntypes,
+                  const int32_t* rlabels, const int32_t* clabels, gdist_group_side* out, int64_t* bad) {
     hipStream_t st = ctx->stream;
-    const int64_t nr = r1 - r0, nc = c1 - c0;
-    const bool sketch = s->kind == GDIST_SKETCH;
-    const bool upper = (flags & GDIST_UPPER_TRIANGLE) != 0;
-    const size_t elem = sketch ? 8 : 4;
-    const int empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
-    const unsigned mflags = flags & (GDIST_EMPTY_NAN | GDIST_SKETCH_JACCARD);
     const size_t nslots = (size_t)ntypes * kTypeSlots;
     std::vector<unsigned long long> h(nslots, 0ull);
-
-    const bool timed = ctx->option(OPT_TIME_KERNELS, 0) != 0;
-    ctx->group_matrix_ms = ctx->group_reduce_ms = -1.0;
-    double matrix_ms = 0, reduce_ms = 0;
-    if (nr > 0 && nc > 0) {
+    if (r1 > r0 && c1 > c0) {
         int64_t R, W;
-        closest_blocks(ctx, nr, nc, elem, &R, &W);
-        DevBuf blk((size_t)R * W * elem + 8, st);
-        DevBuf lab((size_t)ntypes * s->nsets * 4, st), acc(nslots * 8, st);
-        h2d(lab.p, labels, (size_t)ntypes * s->nsets * 4, st);
+        closest_blocks(ctx, r1 - r0, c1 - c0, src.elem(), &R, &W);
+        Walk walk(ctx, src, R, W);
+        const WalkLabels lab(src, ntypes, rlabels, clabels, st);
+        DevBuf acc(nslots * 8, st);
         GD_HIP(hipMemsetAsync(acc.p, 0, nslots * 8, st));
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        struct EvGuard {
-            hipEvent_t* e;
-            ~EvGuard() { for (int i = 0; i < 3; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-        } guard{ev};
-        if (timed) for (auto& e : ev) GD_HIP(hipEventCreate(&e));
-        for (int64_t b0 = r0; b0 < r1; b0 += R) {
-            const int64_t b1 = std::min(r1, b0 + R), nb = b1 - b0;
-            for (int64_t k0 = c0; k0 < c1; k0 += W) {   // any order: the sums do not depend on it
-                const int64_t k1 = std::min(c1, k0 + W), nk = k1 - k0;
-                if (upper && k1 - 1 <= b0) continue;    // wholly on or left of the diagonal
-                if (timed) GD_HIP(hipEventRecord(ev[0], st));
-                if (sketch) {
-                    sketch_matrix(ctx, s, b0, b1, k0, k1, mflags, nullptr, blk.as<double>(), nk);
-                } else if (method == GDIST_METHOD_BITSET) {
-                    zero_counts(ctx, b0, b1, k0, k1, false, blk.as<int32_t>(), nk);
-                    bitset_matrix(ctx, s, b0, b1, k0, k1, false, blk.as<int32_t>(), nk);
-                } else {
-                    sorted_matrix(ctx, s, b0, b1, k0, k1, false, blk.as<int32_t>(), nk);
-                }
-                if (timed) GD_HIP(hipEventRecord(ev[1], st));
-                const dim3 grid = group_grid(ctx, nb, nk, ntypes);
-                const int64_t nseg = ceil_div(nk, kSegCols), nitems = nb * nseg;
-                if (sketch)
-                    group_reduce_kernel<false><<<grid, 256, 0, st>>>(
-                        blk.p, nk, nullptr, nullptr, empty_nan, b0, nb, k0, nk, upper ? 1 : 0, lab.as<int32_t>(),
-                        s->nsets, lab.as<int32_t>(), s->nsets, nitems, nseg, acc.as<unsigned long long>());
-                else
-                    group_reduce_kernel<true><<<grid, 256, 0, st>>>(
-                        blk.p, nk, s->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan, b0, nb, k0, nk, upper ? 1 : 0,
-                        lab.as<int32_t>(), s->nsets, lab.as<int32_t>(), s->nsets, nitems, nseg,
-                        acc.as<unsigned long long>());
-                GD_HIP(hipGetLastError());
-                if (timed) {
-                    GD_HIP(hipEventRecord(ev[2], st));
-                    GD_HIP(hipEventSynchronize(ev[2]));
-                    float m = 0, rd = 0;
-                    GD_HIP(hipEventElapsedTime(&m, ev[0], ev[1]));
-                    GD_HIP(hipEventElapsedTime(&rd, ev[1], ev[2]));
-                    matrix_ms += m;
-                    reduce_ms += rd;
-                }
-            }
-        }
+        const auto kernel = src.from_counts ? group_reduce_kernel<true> : group_reduce_kernel<false>;
+        walk.run(r0, r1, c0, c1, false, [&](const WalkStep& t) {
+            const int64_t nseg = ceil_div(t.nk, kSegCols);
+            kernel<<<group_grid(ctx, t.nb, t.nk, ntypes), 256, 0, st>>>(
+                walk.blk.p, t.nk, src.roff, src.coff, src.empty_nan, t.b0, t.nb, t.k0, t.nk, src.upper, lab.rows,
+                src.nrsets, lab.cols, src.ncsets, t.nb * nseg, nseg, acc.as<unsigned long long>());
+            GD_HIP(hipGetLastError());
+        }, [](const WalkStep&) {});
         d2h(h.data(), acc.p, nslots * 8, st);
     }
-    if (timed) {
-        ctx->group_matrix_ms = matrix_ms;
-        ctx->group_reduce_ms = reduce_ms;
-    }
-
     group_finish(h.data(), ntypes, out, bad);
+}
+
+void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
+                 unsigned flags, int ntypes, const int32_t* labels, gdist_group_side* out, int64_t* bad) {
+    SelfSource src(ctx, s, method, flags);
+    ctx->group_matrix_ms = ctx->group_reduce_ms = -1.0;
+    group_reduce(ctx, src, r0, r1, c0, c1, ntypes, labels, labels, out, bad);
+    if (src.timed) {
+        ctx->group_matrix_ms = src.fill_ms;
+        ctx->group_reduce_ms = src.consume_ms;
+    }
 }
 
 }  // namespace gdist

@@ -173,21 +173,8 @@ dim3 hist_grid(const gdist_ctx* ctx, int64_t nrows, int64_t nc, int passes) {
 
 }  // namespace
 
-size_t hist_slots(int nedges, int ntypes) { return (size_t)std::max(1, ntypes) * ((size_t)2 * (nedges + 1) + 3); }
-
-void hist_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
-                 int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, int ntypes,
-                 const int32_t* d_rlab, int64_t nrsets, const int32_t* d_clab, int64_t ncsets, const double* d_edges,
-                 int nedges, unsigned long long* d_acc) {
-    const dim3 grid = hist_grid(ctx, nrows, nc, std::max(1, ntypes));
-    const int64_t nseg = ceil_div(nc, kSegCols);
-    hist_kernel<true><<<grid, 256, 0, ctx->stream>>>(d_I, ld, d_roff, d_coff, empty_nan, q0, nrows, c0, nc, 0,
-                                                     ntypes ? d_rlab : nullptr, nrsets, ntypes ? d_clab : nullptr,
-                                                     ncsets, nrows * nseg, nseg, d_edges, nedges, d_acc);
-    GD_HIP(hipGetLastError());
-}
-
-void hist_finish(const unsigned long long* h, int nedges, int ntypes, int64_t* counts, int64_t* nans, int64_t* bad) {
+static void hist_finish(const unsigned long long* h, int nedges, int ntypes, int64_t* counts, int64_t* nans,
+                        int64_t* bad) {
     // series 2 t / 2 t + 1 of grouping t; without labels the one series is
     // the in side of the single pass (every label reads as 0)
     const int nb = nedges + 1, passes = std::max(1, ntypes);
@@ -204,84 +191,46 @@ void hist_finish(const unsigned long long* h, int nedges, int ntypes, int64_t* c
     }
 }
 
+// Any order of the steps: the counts do not depend on it.
+void hist_count(gdist_ctx* ctx, WalkSource& src, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int nedges,
+                const double* edges, int ntypes, const int32_t* rlabels, const int32_t* clabels, int64_t* counts,
+                int64_t* nans, int64_t* bad) {
+    hipStream_t st = ctx->stream;
+    const int passes = std::max(1, ntypes);
+    const size_t nslots = (size_t)passes * ((size_t)2 * (nedges + 1) + 3);
+    std::vector<unsigned long long> h(nslots, 0ull);
+    if (r1 > r0 && c1 > c0) {
+        int64_t R, W;
+        closest_blocks(ctx, r1 - r0, c1 - c0, src.elem(), &R, &W);
+        Walk walk(ctx, src, R, W);
+        const WalkLabels lab(src, ntypes, rlabels, clabels, st);   // no labels: null, every pair in one series
+        DevBuf edg((size_t)nedges * 8, st), acc(nslots * 8, st);
+        h2d(edg.p, edges, (size_t)nedges * 8, st);
+        GD_HIP(hipMemsetAsync(acc.p, 0, nslots * 8, st));
+        const auto kernel = src.from_counts ? hist_kernel<true> : hist_kernel<false>;
+        walk.run(r0, r1, c0, c1, false, [&](const WalkStep& t) {
+            const int64_t nseg = ceil_div(t.nk, kSegCols);
+            kernel<<<hist_grid(ctx, t.nb, t.nk, passes), 256, 0, st>>>(
+                walk.blk.p, t.nk, src.roff, src.coff, src.empty_nan, t.b0, t.nb, t.k0, t.nk, src.upper, lab.rows,
+                src.nrsets, lab.cols, src.ncsets, t.nb * nseg, nseg, edg.as<double>(), nedges,
+                acc.as<unsigned long long>());
+            GD_HIP(hipGetLastError());
+        }, [](const WalkStep&) {});
+        d2h(h.data(), acc.p, nslots * 8, st);
+    }
+    hist_finish(h.data(), nedges, ntypes, counts, nans, bad);
+}
+
 void histogram(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
                unsigned flags, int nedges, const double* edges, int ntypes, const int32_t* labels, int64_t* counts,
                int64_t* nans, int64_t* bad) {
-    hipStream_t st = ctx->stream;
-    const int64_t nr = r1 - r0, nc = c1 - c0;
-    const bool sketch = s->kind == GDIST_SKETCH;
-    const bool upper = (flags & GDIST_UPPER_TRIANGLE) != 0;
-    const size_t elem = sketch ? 8 : 4;
-    const int empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
-    const unsigned mflags = flags & (GDIST_EMPTY_NAN | GDIST_SKETCH_JACCARD);
-    const int nb = nedges + 1, passes = std::max(1, ntypes);
-    const size_t tslots = (size_t)2 * nb + 3, nslots = (size_t)passes * tslots;
-    std::vector<unsigned long long> h(nslots, 0ull);
-
-    const bool timed = ctx->option(OPT_TIME_KERNELS, 0) != 0;
+    SelfSource src(ctx, s, method, flags);
     ctx->hist_matrix_ms = ctx->hist_reduce_ms = -1.0;
-    double matrix_ms = 0, reduce_ms = 0;
-    if (nr > 0 && nc > 0) {
-        int64_t R, W;
-        closest_blocks(ctx, nr, nc, elem, &R, &W);
-        DevBuf blk((size_t)R * W * elem + 8, st);
-        DevBuf lab((size_t)ntypes * s->nsets * 4, st), edg((size_t)nedges * 8, st), acc(nslots * 8, st);
-        h2d(lab.p, labels, (size_t)ntypes * s->nsets * 4, st);
-        h2d(edg.p, edges, (size_t)nedges * 8, st);
-        GD_HIP(hipMemsetAsync(acc.p, 0, nslots * 8, st));
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        struct EvGuard {
-            hipEvent_t* e;
-            ~EvGuard() { for (int i = 0; i < 3; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-        } guard{ev};
-        if (timed) for (auto& e : ev) GD_HIP(hipEventCreate(&e));
-        for (int64_t b0 = r0; b0 < r1; b0 += R) {
-            const int64_t b1 = std::min(r1, b0 + R), nbr = b1 - b0;
-            for (int64_t k0 = c0; k0 < c1; k0 += W) {   // any order: the counts do not depend on it
-                const int64_t k1 = std::min(c1, k0 + W), nk = k1 - k0;
-                if (upper && k1 - 1 <= b0) continue;    // wholly on or left of the diagonal
-                if (timed) GD_HIP(hipEventRecord(ev[0], st));
-                if (sketch) {
-                    sketch_matrix(ctx, s, b0, b1, k0, k1, mflags, nullptr, blk.as<double>(), nk);
-                } else if (method == GDIST_METHOD_BITSET) {
-                    zero_counts(ctx, b0, b1, k0, k1, false, blk.as<int32_t>(), nk);
-                    bitset_matrix(ctx, s, b0, b1, k0, k1, false, blk.as<int32_t>(), nk);
-                } else {
-                    sorted_matrix(ctx, s, b0, b1, k0, k1, false, blk.as<int32_t>(), nk);
-                }
-                if (timed) GD_HIP(hipEventRecord(ev[1], st));
-                const dim3 grid = hist_grid(ctx, nbr, nk, passes);
-                const int64_t nseg = ceil_div(nk, kSegCols), nitems = nbr * nseg;
-                const int32_t* dl = ntypes ? lab.as<int32_t>() : nullptr;
-                if (sketch)
-                    hist_kernel<false><<<grid, 256, 0, st>>>(
-                        blk.p, nk, nullptr, nullptr, empty_nan, b0, nbr, k0, nk, upper ? 1 : 0, dl, s->nsets, dl,
-                        s->nsets, nitems, nseg, edg.as<double>(), nedges, acc.as<unsigned long long>());
-                else
-                    hist_kernel<true><<<grid, 256, 0, st>>>(
-                        blk.p, nk, s->off.as<int64_t>(), s->off.as<int64_t>(), empty_nan, b0, nbr, k0, nk,
-                        upper ? 1 : 0, dl, s->nsets, dl, s->nsets, nitems, nseg, edg.as<double>(), nedges,
-                        acc.as<unsigned long long>());
-                GD_HIP(hipGetLastError());
-                if (timed) {
-                    GD_HIP(hipEventRecord(ev[2], st));
-                    GD_HIP(hipEventSynchronize(ev[2]));
-                    float m = 0, rd = 0;
-                    GD_HIP(hipEventElapsedTime(&m, ev[0], ev[1]));
-                    GD_HIP(hipEventElapsedTime(&rd, ev[1], ev[2]));
-                    matrix_ms += m;
-                    reduce_ms += rd;
-                }
-            }
-        }
-        d2h(h.data(), acc.p, nslots * 8, st);
+    hist_count(ctx, src, r0, r1, c0, c1, nedges, edges, ntypes, labels, labels, counts, nans, bad);
+    if (src.timed) {
+        ctx->hist_matrix_ms = src.fill_ms;
+        ctx->hist_reduce_ms = src.consume_ms;
     }
-    if (timed) {
-        ctx->hist_matrix_ms = matrix_ms;
-        ctx->hist_reduce_ms = reduce_ms;
-    }
-
-    hist_finish(h.data(), nedges, ntypes, counts, nans, bad);
 }
 
 }  // namespace gdist

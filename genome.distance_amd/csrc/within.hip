@@ -193,142 +193,74 @@ int64_t within_rows(const gdist_ctx* ctx, int64_t nr, int64_t nc, size_t elem) {
     return std::min<int64_t>(R, std::max<int64_t>(nr, 1));
 }
 
-int64_t within_tiles(int64_t nrows, int64_t nc) { return nrows * ceil_div(nc, kSegCols); }
-
-void within_count_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
-                         int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, double max_dist,
-                         int32_t* d_tcount, int64_t* d_tbase, int64_t* d_rbase, DevBuf& scan_tmp) {
-    hipStream_t st = ctx->stream;
-    const int64_t nseg = ceil_div(nc, kSegCols), ntiles = nrows * nseg;
-    within_count_kernel<true><<<(unsigned)ceil_div(ntiles, 4), 256, 0, st>>>(
-        d_I, ld, d_roff, d_coff, empty_nan, q0, c0, nc, 1, 0, max_dist, ntiles, nseg, d_tcount);
-    GD_HIP(hipGetLastError());
-    // ntiles + 1 elements: the step's total lands at d_tbase[ntiles]
-    scan_counts(st, d_tcount, d_tbase, (size_t)ntiles + 1, scan_tmp);
-    within_row_base_kernel<<<(unsigned)ceil_div(nrows + 1, 256), 256, 0, st>>>(d_tbase, nseg, nrows, d_rbase);
-    GD_HIP(hipGetLastError());
-}
-
-void within_write_counts(gdist_ctx* ctx, const int32_t* d_I, int64_t ld, const int64_t* d_roff, const int64_t* d_coff,
-                         int empty_nan, int64_t q0, int64_t nrows, int64_t c0, int64_t nc, double max_dist,
-                         const int64_t* d_tbase, int64_t fit, int64_t* d_col, double* d_d) {
-    const int64_t nseg = ceil_div(nc, kSegCols), ntiles = nrows * nseg;
-    within_write_kernel<true><<<(unsigned)ceil_div(ntiles, 4), 256, 0, ctx->stream>>>(
-        d_I, ld, d_roff, d_coff, empty_nan, q0, c0, nc, 1, 0, max_dist, ntiles, nseg, d_tbase, fit, d_col, d_d);
-    GD_HIP(hipGetLastError());
-}
-
-// method: SORTED or BITSET (resolved by the caller); ignored for sketches.
-// rowptr: nr + 1 entries, written whole. col_out / d_out: the first
-// min(total, capacity) entries.
-void within(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
-            unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr, int64_t* col_out, double* d_out) {
+// The steps arrive in row order and a step spans the call's columns, so its
+// survivors are already in output order. rowptr: r1 - r0 + 1 entries, written
+// whole. col_out / d_out: the first min(total, capacity) entries.
+void within_compact(gdist_ctx* ctx, WalkSource& src, int64_t r0, int64_t r1, int64_t c0, int64_t c1, double max_dist,
+                    int64_t capacity, int64_t* rowptr, int64_t* col_out, double* d_out) {
     hipStream_t st = ctx->stream;
     const int64_t nr = r1 - r0, nc = c1 - c0;
-    const bool sketch = s->kind == GDIST_SKETCH;
-    const bool upper = (flags & GDIST_UPPER_TRIANGLE) != 0;
-    const size_t elem = sketch ? 8 : 4;
-    const int keep_self = (flags & GDIST_CLOSEST_KEEP_SELF) ? 1 : 0;
-    const int empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
-    const unsigned mflags = flags & (GDIST_EMPTY_NAN | GDIST_SKETCH_JACCARD);
-    // option time_kernels: the matrix kernels and the count / scan / write
-    // kernels of every step apart (gdist_ctx_within_timing)
-    const bool timed = ctx->option(OPT_TIME_KERNELS, 0) != 0;
-    ctx->within_matrix_ms = ctx->within_select_ms = -1.0;
-    double matrix_ms = 0, select_ms = 0;
-    rowptr[0] = 0;
-    if (nr == 0) return;
-    if (nc == 0) {
-        std::fill(rowptr, rowptr + nr + 1, (int64_t)0);
-        return;
-    }
-    const int64_t R = within_rows(ctx, nr, nc, elem);
+    const int64_t R = within_rows(ctx, nr, nc, src.elem());
+    Walk walk(ctx, src, R, nc);
     const int64_t max_tiles = R * ceil_div(nc, kSegCols);
-    DevBuf blk((size_t)R * nc * elem + 8, st);
     DevBuf tcount((size_t)(max_tiles + 1) * 4, st), tbase((size_t)(max_tiles + 1) * 8, st);
     DevBuf rbase((size_t)(R + 1) * 8, st), scan_tmp;
     std::vector<int64_t> hbase((size_t)R + 1);
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() { for (int i = 0; i < 5; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-    } guard{ev};
-    if (timed) for (auto& e : ev) GD_HIP(hipEventCreate(&e));
+    const auto count = src.from_counts ? within_count_kernel<true> : within_count_kernel<false>;
+    const auto write = src.from_counts ? within_write_kernel<true> : within_write_kernel<false>;
     int64_t total = 0;   // pairs of the rows before this step
-    for (int64_t b0 = r0; b0 < r1; b0 += R) {
-        const int64_t b1 = std::min(r1, b0 + R), nb = b1 - b0;
-        const int64_t k0 = upper ? std::max(c0, b0 + 1) : c0, nk = c1 - k0;
-        int64_t* rp = rowptr + (b0 - r0);
-        if (nk <= 0) {   // the block lies wholly on or left of the diagonal
-            std::fill(rp, rp + nb + 1, total);
-            continue;
-        }
-        if (timed) GD_HIP(hipEventRecord(ev[0], st));
-        if (sketch) {
-            sketch_matrix(ctx, s, b0, b1, k0, c1, mflags, nullptr, blk.as<double>(), nk);
-        } else if (method == GDIST_METHOD_BITSET) {
-            zero_counts(ctx, b0, b1, k0, c1, false, blk.as<int32_t>(), nk);
-            bitset_matrix(ctx, s, b0, b1, k0, c1, false, blk.as<int32_t>(), nk);
-        } else {
-            sorted_matrix(ctx, s, b0, b1, k0, c1, false, blk.as<int32_t>(), nk);
-        }
-        if (timed) GD_HIP(hipEventRecord(ev[1], st));
-        const int64_t nseg = ceil_div(nk, kSegCols), ntiles = nb * nseg;
-        const unsigned grid = (unsigned)ceil_div(ntiles, 4);
-        const int64_t* off = sketch ? nullptr : s->off.as<int64_t>();
-        if (sketch)
-            within_count_kernel<false><<<grid, 256, 0, st>>>(blk.p, nk, off, off, empty_nan, b0, k0, nk, keep_self,
-                                                             upper ? 1 : 0, max_dist, ntiles, nseg,
-                                                             tcount.as<int32_t>());
-        else
-            within_count_kernel<true><<<grid, 256, 0, st>>>(blk.p, nk, off, off, empty_nan, b0, k0, nk, keep_self,
-                                                            upper ? 1 : 0, max_dist, ntiles, nseg,
-                                                            tcount.as<int32_t>());
+    int64_t done = 0;    // rows whose rowptr entries are written
+    rowptr[0] = 0;
+    walk.run(r0, r1, c0, c1, true, [&](const WalkStep& t) {
+        const int64_t nseg = ceil_div(t.nk, kSegCols), ntiles = t.nb * nseg;
+        count<<<(unsigned)ceil_div(ntiles, 4), 256, 0, st>>>(walk.blk.p, t.nk, src.roff, src.coff, src.empty_nan, t.b0,
+                                                             t.k0, t.nk, src.keep_self, src.upper, max_dist, ntiles,
+                                                             nseg, tcount.as<int32_t>());
         GD_HIP(hipGetLastError());
         // ntiles + 1 elements: the step's total lands at tbase[ntiles] (the
         // last input is not part of any exclusive sum)
         scan_counts(st, tcount.as<int32_t>(), tbase.as<int64_t>(), (size_t)ntiles + 1, scan_tmp);
-        within_row_base_kernel<<<(unsigned)ceil_div(nb + 1, 256), 256, 0, st>>>(tbase.as<int64_t>(), nseg, nb,
-                                                                              rbase.as<int64_t>());
+        within_row_base_kernel<<<(unsigned)ceil_div(t.nb + 1, 256), 256, 0, st>>>(tbase.as<int64_t>(), nseg, t.nb,
+                                                                                rbase.as<int64_t>());
         GD_HIP(hipGetLastError());
-        if (timed) GD_HIP(hipEventRecord(ev[2], st));
-        d2h(hbase.data(), rbase.p, (size_t)(nb + 1) * 8, st);
-        for (int64_t a = 0; a <= nb; a++) rp[a] = total + hbase[a];
-        const int64_t step = hbase[nb];
+    }, [&](const WalkStep& t) {
+        d2h(hbase.data(), rbase.p, (size_t)(t.nb + 1) * 8, st);
+        int64_t* rp = rowptr + (t.b0 - r0);
+        for (int64_t a = 0; a <= t.nb; a++) rp[a] = total + hbase[a];
+        const int64_t step = hbase[t.nb];
         const int64_t fit = std::min(step, std::max<int64_t>(capacity - total, 0));
         if (fit > 0) {
+            const int64_t nseg = ceil_div(t.nk, kSegCols), ntiles = t.nb * nseg;
             DevBuf sc((size_t)fit * 8, st), sd((size_t)fit * 8, st);
-            if (timed) GD_HIP(hipEventRecord(ev[3], st));
-            if (sketch)
-                within_write_kernel<false><<<grid, 256, 0, st>>>(
-                    blk.p, nk, off, off, empty_nan, b0, k0, nk, keep_self, upper ? 1 : 0, max_dist, ntiles, nseg,
-                    tbase.as<int64_t>(), fit, sc.as<int64_t>(), sd.as<double>());
-            else
-                within_write_kernel<true><<<grid, 256, 0, st>>>(
-                    blk.p, nk, off, off, empty_nan, b0, k0, nk, keep_self, upper ? 1 : 0, max_dist, ntiles, nseg,
-                    tbase.as<int64_t>(), fit, sc.as<int64_t>(), sd.as<double>());
-            GD_HIP(hipGetLastError());
-            if (timed) GD_HIP(hipEventRecord(ev[4], st));
+            walk.timed_select([&] {
+                write<<<(unsigned)ceil_div(ntiles, 4), 256, 0, st>>>(
+                    walk.blk.p, t.nk, src.roff, src.coff, src.empty_nan, t.b0, t.k0, t.nk, src.keep_self, src.upper,
+                    max_dist, ntiles, nseg, tbase.as<int64_t>(), fit, sc.as<int64_t>(), sd.as<double>());
+                GD_HIP(hipGetLastError());
+            });
             d2h(col_out + total, sc.p, (size_t)fit * 8, st);
             d2h(d_out + total, sd.p, (size_t)fit * 8, st);
         }
-        if (timed) {
-            GD_HIP(hipEventSynchronize(ev[2]));
-            float m = 0, c = 0, w = 0;
-            GD_HIP(hipEventElapsedTime(&m, ev[0], ev[1]));
-            GD_HIP(hipEventElapsedTime(&c, ev[1], ev[2]));
-            if (fit > 0) {
-                GD_HIP(hipEventSynchronize(ev[4]));
-                GD_HIP(hipEventElapsedTime(&w, ev[3], ev[4]));
-            }
-            matrix_ms += m;
-            select_ms += c + w;
-        }
         total += step;
-    }
-    if (timed) {
-        ctx->within_matrix_ms = matrix_ms;
-        ctx->within_select_ms = select_ms;
+        done = t.b0 - r0 + t.nb;
+    });
+    // the row blocks wholly on or left of the diagonal (the last ones) had no step
+    std::fill(rowptr + done + 1, rowptr + nr + 1, total);
+}
+
+// method: SORTED or BITSET (resolved by the caller); ignored for sketches.
+void within(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int method,
+            unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr, int64_t* col_out, double* d_out) {
+    ctx->within_matrix_ms = ctx->within_select_ms = -1.0;
+    std::fill(rowptr, rowptr + (r1 - r0) + 1, (int64_t)0);
+    if (r1 == r0 || c1 == c0) return;
+    SelfSource src(ctx, s, method, flags);
+    within_compact(ctx, src, r0, r1, c0, c1, max_dist, capacity, rowptr, col_out, d_out);
+    // option time_kernels: the matrix kernels and the count / scan / write
+    // kernels of every step apart (gdist_ctx_within_timing)
+    if (src.timed) {
+        ctx->within_matrix_ms = src.fill_ms;
+        ctx->within_select_ms = src.consume_ms;
     }
 }
 

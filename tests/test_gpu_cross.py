@@ -137,6 +137,25 @@ def test_sub_rectangle_and_padding(subj, qry, want):
         assert np.all(D == POISON_D)
 
 
+@pytest.mark.parametrize("flags", [0, EMPTY_NAN], ids=["plain", "empty_nan"])
+def test_matrix_walk_cuts(subj, qry, opts, flags):
+    """closest_rows 4 x closest_cols 4 over rows (1, 10) x cols (0, 10): row
+    blocks of 4, 4 and 1 rows against column chunks of 4, 4 and 2 columns, nine
+    steps. The arrays, padding included, are the bytes of the one-step call and
+    the cells are the oracle's."""
+    rows, cols = (1, 10), (0, 10)
+    eI, eD = X.expected(flags)
+    rc, I1, D1 = raw_matrix(subj, qry, rows, cols, flags, pad=3)
+    assert rc == 0
+    opts(closest_rows=4, closest_cols=4)
+    rc, I, D = raw_matrix(subj, qry, rows, cols, flags, pad=3)
+    assert rc == 0
+    assert I.tobytes() == I1.tobytes() and D.tobytes() == D1.tobytes()
+    assert np.all(I[:, 10:] == POISON_I) and np.all(D[:, 10:] == POISON_D)
+    assert np.array_equal(I[:, :10], eI[1:10, 0:10])
+    assert np.array_equal(bits(D[:, :10]), bits(eD[1:10, 0:10]))
+
+
 # 3 ---------------------------------------------------------------------------
 def test_same_handle_for_both(subj):
     import gdist

@@ -338,6 +338,12 @@ def test_sketches(sketch_case, opts, width, flags):
     check(sk, D, 0.9, rows=(100, 121), cols=(0, 100), flags=flags)
     got = sk.within(0.9, rows=(100, 121), cols=(0, 100), flags=flags)
     assert same_bytes(got, R.within_ref(D[100:121, 0:100], 0.9, 100, 0))
+    # upper, still 50 rows a block: rows 60..109 straddle the diagonal of the
+    # columns (0, 100), rows 110..120 lie wholly left of it and have no step
+    cut = check(sk, D, 0.9, rows=(60, 121), cols=(0, 100), flags=flags | UPPER_TRIANGLE)
+    assert 0 < cut[0][50] and np.all(cut[0][50:] == cut[0][50])
+    opts(closest_rows=None)
+    assert same_bytes(cut, check(sk, D, 0.9, rows=(60, 121), cols=(0, 100), flags=flags | UPPER_TRIANGLE))
 
 
 def test_errors_and_edge_cases(kset, ctx):
