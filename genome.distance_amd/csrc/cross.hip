@@ -33,6 +33,10 @@
 // and the bucket counts of hist.hip (gdist_cross_histogram). Each is the
 // kernel its one-collection twin runs, given the queries' offsets and labels
 // for the rows and the subjects' for the columns.
+//
+// Two sketch collections take the same consumers over another source
+// (SketchCrossSource, sketch_cross.hip), whose steps hold distances; nothing
+// above (segment index, units, join, epilogue) runs for them.
 #include <algorithm>
 #include <cstring>
 
@@ -240,76 +244,111 @@ struct CrossSource : WalkSource {
 
 static_assert(sizeof(CrossUnit) == sizeof(int4), "units are uploaded as 16-byte records");
 
-// every argument checked by the caller, the subjects' segment index built;
-// I_out / D_out: host, row stride ld, either may be null
+namespace {
+
+// the source of the pair's kind: kmer sets join by the segment index, sketches
+// merge (sketch_cross.hip); f(src) runs the walk and reports
+template <class F>
+void with_source(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, unsigned flags, F&& f) {
+    if (q->kind == GDIST_SKETCH) {
+        SketchCrossSource src(ctx, q, s, flags);
+        f(src);
+    } else {
+        CrossSource src(ctx, q, s, flags);
+        f(src);
+    }
+}
+
+}  // namespace
+
+// every argument checked by the caller, kmer sets: the subjects' segment index
+// built; I_out / D_out: host, row stride ld, either may be null. Sketches: I
+// is the common count, and D comes from the merge kernel itself (no epilogue)
 void cross_matrix(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
                   int64_t c1, unsigned flags, int32_t* I_out, double* D_out, int64_t ld) {
     hipStream_t st = ctx->stream;
-    CrossSource src(ctx, q, s, flags);
     int64_t R, W;
     closest_blocks(ctx, q1 - q0, c1 - c0, 12, &R, &W);   // a step's I and D
-    Walk walk(ctx, src, R, W);
     DevBuf dD;
     if (D_out) dD.alloc((size_t)R * W * 8 + 8, st);
     std::vector<int32_t> hI;
     std::vector<double> hD;
-    walk.run(q0, q1, c0, c1, false, [&](const WalkStep& t) {
+    auto run = [&](auto& src, auto&& epilogue) {
+        Walk walk(ctx, src, R, W);
+        walk.run(q0, q1, c0, c1, false, [&](const WalkStep& t) { epilogue(walk, t); }, [&](const WalkStep& t) {
+            const size_t cells = (size_t)t.nb * t.nk;
+            if (D_out) {
+                hD.resize(cells);
+                d2h(hD.data(), dD.p, cells * 8, st);
+                for (int64_t a = 0; a < t.nb; a++)
+                    std::memcpy(D_out + (t.b0 - q0 + a) * ld + (t.k0 - c0), hD.data() + (size_t)a * t.nk,
+                                (size_t)t.nk * 8);
+            }
+            if (I_out) {
+                hI.resize(cells);
+                d2h(hI.data(), walk.blk.p, cells * 4, st);
+                for (int64_t a = 0; a < t.nb; a++)
+                    std::memcpy(I_out + (t.b0 - q0 + a) * ld + (t.k0 - c0), hI.data() + (size_t)a * t.nk,
+                                (size_t)t.nk * 4);
+            }
+        });
+        src.report();
+    };
+    if (q->kind == GDIST_SKETCH) {
+        SketchCrossSource src(ctx, q, s, flags);
+        src.matrix = true;
+        src.want_common = I_out != nullptr;
+        src.d_to = dD.as<double>();
+        run(src, [](Walk&, const WalkStep&) {});
+        return;
+    }
+    CrossSource src(ctx, q, s, flags);
+    run(src, [&](Walk& walk, const WalkStep& t) {
         if (!D_out) return;
         const int64_t cells = t.nb * t.nk;
         const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(cells, 256), (int64_t)ctx->cus * 16);
         cross_epilogue_kernel<<<grid, 256, 0, st>>>(src.roff, src.coff, t.b0, t.nb, t.k0, t.nk, src.empty_nan,
                                                     walk.blk.as<int32_t>(), dD.as<double>());
         GD_HIP(hipGetLastError());
-    }, [&](const WalkStep& t) {
-        const size_t cells = (size_t)t.nb * t.nk;
-        if (D_out) {
-            hD.resize(cells);
-            d2h(hD.data(), dD.p, cells * 8, st);
-            for (int64_t a = 0; a < t.nb; a++)
-                std::memcpy(D_out + (t.b0 - q0 + a) * ld + (t.k0 - c0), hD.data() + (size_t)a * t.nk, (size_t)t.nk * 8);
-        }
-        if (I_out) {
-            hI.resize(cells);
-            d2h(hI.data(), walk.blk.p, cells * 4, st);
-            for (int64_t a = 0; a < t.nb; a++)
-                std::memcpy(I_out + (t.b0 - q0 + a) * ld + (t.k0 - c0), hI.data() + (size_t)a * t.nk, (size_t)t.nk * 4);
-        }
     });
-    src.report();
 }
 
-// The twins: the one-collection call's consumer over a CrossSource. closest
+// The twins: the one-collection call's consumer over the pair's source. closest
 // and within: a non-empty rectangle (n >= 1); group_stats and histogram: any
 void cross_closest(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
                    int64_t c1, unsigned flags, int n, double max_dist, int64_t* idx_out, double* d_out,
                    int32_t* count_out) {
-    CrossSource src(ctx, q, s, flags);
-    closest_select(ctx, src, q0, q1, c0, c1, n, max_dist, idx_out, d_out, count_out);
-    src.report();
+    with_source(ctx, q, s, flags, [&](auto& src) {
+        closest_select(ctx, src, q0, q1, c0, c1, n, max_dist, idx_out, d_out, count_out);
+        src.report();
+    });
 }
 
 void cross_within(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
                   int64_t c1, unsigned flags, double max_dist, int64_t capacity, int64_t* rowptr, int64_t* col_out,
                   double* d_out) {
-    CrossSource src(ctx, q, s, flags);
-    within_compact(ctx, src, q0, q1, c0, c1, max_dist, capacity, rowptr, col_out, d_out);
-    src.report();
+    with_source(ctx, q, s, flags, [&](auto& src) {
+        within_compact(ctx, src, q0, q1, c0, c1, max_dist, capacity, rowptr, col_out, d_out);
+        src.report();
+    });
 }
 
 void cross_group_stats(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
                        int64_t c1, unsigned flags, int ntypes, const int32_t* qlabels, const int32_t* slabels,
                        gdist_group_side* out, int64_t* bad) {
-    CrossSource src(ctx, q, s, flags);
-    group_reduce(ctx, src, q0, q1, c0, c1, ntypes, qlabels, slabels, out, bad);
-    if (q1 > q0 && c1 > c0) src.report();
+    with_source(ctx, q, s, flags, [&](auto& src) {
+        group_reduce(ctx, src, q0, q1, c0, c1, ntypes, qlabels, slabels, out, bad);
+        if (q1 > q0 && c1 > c0) src.report();
+    });
 }
 
 void cross_histogram(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, int64_t q0, int64_t q1, int64_t c0,
                      int64_t c1, unsigned flags, int nedges, const double* edges, int ntypes, const int32_t* qlabels,
                      const int32_t* slabels, int64_t* counts, int64_t* nans, int64_t* bad) {
-    CrossSource src(ctx, q, s, flags);
-    hist_count(ctx, src, q0, q1, c0, c1, nedges, edges, ntypes, qlabels, slabels, counts, nans, bad);
-    if (q1 > q0 && c1 > c0) src.report();
+    with_source(ctx, q, s, flags, [&](auto& src) {
+        hist_count(ctx, src, q0, q1, c0, c1, nedges, edges, ntypes, qlabels, slabels, counts, nans, bad);
+        if (q1 > q0 && c1 > c0) src.report();
+    });
 }
 
 }  // namespace gdist

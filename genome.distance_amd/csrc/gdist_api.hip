@@ -1459,15 +1459,26 @@ static void check_cross(gdist_ctx* ctx, const gdist_sets* queries, const gdist_s
     check_sets(queries);
     check_sets(subjects);
     GD_REQUIRE(queries->ctx == ctx && subjects->ctx == ctx, "sets belong to another context");
-    GD_REQUIRE(queries->kind != GDIST_SKETCH && subjects->kind != GDIST_SKETCH,
-               "cross calls run on kmer sets (sketches: gdist_lsh_closest)");
+    const bool sketches = queries->kind == GDIST_SKETCH;
+    GD_REQUIRE(sketches == (subjects->kind == GDIST_SKETCH),
+               "cross calls run on kmer sets (or on two sketch collections, never one of each)");
     check_same_spec(queries, subjects);
     check_codes(queries);
     check_codes(subjects);
     GD_REQUIRE(0 <= q0 && q0 <= q1 && q1 <= queries->nsets, "query range outside the query collection");
     GD_REQUIRE(0 <= c0 && c0 <= c1 && c1 <= subjects->nsets, "column range outside the subject collection");
-    GD_REQUIRE(!(flags & ~GDIST_EMPTY_NAN), "cross calls take no flag but GDIST_EMPTY_NAN");
+    if (sketches)
+        GD_REQUIRE(!(flags & ~(GDIST_EMPTY_NAN | GDIST_SKETCH_JACCARD)),
+                   "cross calls on sketches take no flag but GDIST_EMPTY_NAN and GDIST_SKETCH_JACCARD");
+    else
+        GD_REQUIRE(!(flags & ~GDIST_EMPTY_NAN), "cross calls take no flag but GDIST_EMPTY_NAN");
     GD_REQUIRE(subjects->nsets < (int64_t)UINT32_MAX, "too many subjects for 32-bit column keys");
+}
+
+// the one thing a cross call may add to kmer-set subjects, as a SORTED call on
+// them does; sketch subjects stay as they are
+static void cross_index(gdist_ctx* ctx, gdist_sets* s) {
+    if (s->kind != GDIST_SKETCH && !s->segoff.p) build_segments(ctx, s);
 }
 
 static void begin_cross(gdist_ctx* ctx) {
@@ -1642,8 +1653,7 @@ int gdist_cross_matrix(gdist_ctx* ctx, const gdist_sets* queries, const gdist_se
         auto* s = const_cast<gdist_sets*>(subjects);
         begin_cross(ctx);
         if (nr == 0 || nc == 0) return;
-        // the one thing a cross call may add to the subjects, as a SORTED call on them does
-        if (!s->segoff.p) build_segments(ctx, s);
+        cross_index(ctx, s);
         gdist::cross_matrix(ctx, queries, s, q0, q1, c0, c1, flags, I_out, D_out, ld);
     });
 }
@@ -1663,7 +1673,7 @@ int gdist_cross_closest(gdist_ctx* ctx, const gdist_sets* queries, const gdist_s
         begin_cross(ctx);
         if (nr == 0) return;
         if (n == 0 || nc == 0) return closest_none(nr, n, idx_out, d_out, count_out);
-        if (!s->segoff.p) build_segments(ctx, s);
+        cross_index(ctx, s);
         gdist::cross_closest(ctx, queries, s, q0, q1, c0, c1, flags, n, max_dist, idx_out, d_out, count_out);
     });
 }
@@ -1685,7 +1695,7 @@ int gdist_cross_within(gdist_ctx* ctx, const gdist_sets* queries, const gdist_se
         // the row pointers into a local first: a failure on the device leaves them and *total untouched
         std::vector<int64_t> rp((size_t)nr + 1, 0);
         if (nr > 0 && nc > 0) {
-            if (!s->segoff.p) build_segments(ctx, s);
+            cross_index(ctx, s);
             gdist::cross_within(ctx, queries, s, q0, q1, c0, c1, flags, max_dist, capacity, rp.data(), col_out, d_out);
         }
         std::copy(rp.begin(), rp.end(), rowptr_out);
@@ -1704,7 +1714,7 @@ int gdist_cross_group_stats(gdist_ctx* ctx, const gdist_sets* queries, const gdi
         GD_REQUIRE(qlabels && slabels && out && bad, "null labels or output");
         auto* s = const_cast<gdist_sets*>(subjects);
         begin_cross(ctx);
-        if (q1 > q0 && c1 > c0 && !s->segoff.p) build_segments(ctx, s);
+        if (q1 > q0 && c1 > c0) cross_index(ctx, s);
         // into locals first: a failure on the device leaves the outputs untouched too
         std::vector<gdist_group_side> o((size_t)2 * ntypes);
         std::vector<int64_t> b((size_t)ntypes);
@@ -1729,7 +1739,7 @@ int gdist_cross_histogram(gdist_ctx* ctx, const gdist_sets* queries, const gdist
         check_edges(nedges, edges);
         auto* s = const_cast<gdist_sets*>(subjects);
         begin_cross(ctx);
-        if (q1 > q0 && c1 > c0 && !s->segoff.p) build_segments(ctx, s);
+        if (q1 > q0 && c1 > c0) cross_index(ctx, s);
         // into locals first: a failure on the device leaves the outputs untouched too
         const size_t series = ntypes ? (size_t)2 * ntypes : 1;
         std::vector<int64_t> cn(series * ((size_t)nedges + 1)), na(series), b((size_t)ntypes);

@@ -732,7 +732,7 @@ void distance_epilogue(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t 
 //
 // What fills a step, and what the consumers' kernels need to read it: one
 // collection against itself (SelfSource) or queries against subjects
-// (CrossSource, cross.hip). A twin differs from its one-collection call by
+// (CrossSource, cross.hip; sketches: SketchCrossSource, sketch_cross.hip). A twin differs from its one-collection call by
 // nothing but its source.
 struct WalkSource {
     bool from_counts = true;   // a block holds intersection counts (int32); else distances (double)
@@ -760,6 +760,24 @@ struct SelfSource : WalkSource {
     unsigned mflags;
     SelfSource(gdist_ctx* c, const gdist_sets* sets, int method, unsigned flags);
     void fill(int64_t b0, int64_t b1, int64_t k0, int64_t k1, void* blk) override;
+};
+
+// Query sketches against subject sketches (sketch_cross.hip): a step's block
+// takes distances from the wave-per-pair merge kernel. Nothing is built or
+// kept on either collection. matrix (gdist_cross_matrix): the block takes the
+// common counts (want_common) and d_to, of the block's extent, the distances.
+struct SketchCrossSource : WalkSource {
+    gdist_ctx* ctx;
+    const gdist_sets* q;
+    const gdist_sets* s;
+    int jaccard;
+    bool matrix = false, want_common = false;
+    double* d_to = nullptr;
+    int64_t pairs = 0;   // (query, subject) pairs merged so far
+    SketchCrossSource(gdist_ctx* c, const gdist_sets* queries, const gdist_sets* subjects, unsigned flags);
+    void fill(int64_t b0, int64_t b1, int64_t k0, int64_t k1, void* blk) override;
+    // gdist_ctx_cross_info, after a walk
+    void report() const;
 };
 
 // rows [b0, b0 + nb) x columns [k0, k0 + nk); last: the row block's last chunk

@@ -592,6 +592,109 @@ class _Handle:
                 return rowptr, col[:m], d[:m]
             cap = total.value
 
+    # the gdist_cross_* calls behind KmerSets.cross_* and SketchSets.cross_*: `queries` (rows) against this
+    # resident collection (cols)
+    def _cross_matrix(self, queries, rows, cols, flags: int, want_I: bool, want_D: bool):
+        r0, r1 = rows or (0, len(queries))
+        c0, c1 = cols or (0, len(self))
+        nr, nc = max(r1 - r0, 0), max(c1 - c0, 0)
+        I = np.full((nr, nc), -1, dtype=np.int32) if want_I else None
+        D = np.full((nr, nc), np.nan, dtype=np.float64) if want_D else None
+        L.check(L.lib.gdist_cross_matrix(self.ctx.h, queries.h, self.h, r0, r1, c0, c1, flags,
+                                         L.ptr(I, C.c_int32) if want_I else None,
+                                         L.ptr(D, C.c_double) if want_D else None, max(nc, 1)))
+        return I, D
+
+    def _cross_closest(self, queries, n: int, max_dist: float, rows, cols, flags: int):
+        r0, r1 = rows or (0, len(queries))
+        c0, c1 = cols or (0, len(self))
+        nr = max(r1 - r0, 0)
+        idx = np.full((nr, max(n, 0)), -1, dtype=np.int64)
+        d = np.ones((nr, max(n, 0)), dtype=np.float64)
+        cnt = np.zeros(nr, dtype=np.int32)
+        # non-empty buffers behind empty results: the library is never handed a null output
+        bi = idx if idx.size else np.zeros(1, dtype=np.int64)
+        bd = d if d.size else np.zeros(1, dtype=np.float64)
+        bc = cnt if cnt.size else np.zeros(1, dtype=np.int32)
+        L.check(L.lib.gdist_cross_closest(self.ctx.h, queries.h, self.h, r0, r1, c0, c1, flags, int(n),
+                                          float(max_dist), L.ptr(bi, C.c_int64), L.ptr(bd, C.c_double),
+                                          L.ptr(bc, C.c_int32)))
+        return idx, d, cnt
+
+    @staticmethod
+    def _cross_labels(labels, n: int, what: str) -> np.ndarray:
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.ndim == 1:
+            lab = lab[None, :]
+        if lab.ndim != 2 or lab.shape[1] != n:
+            raise ValueError(f"{what} must be [T, {n}] or [{n}], not {list(lab.shape)}")
+        if not 1 <= lab.shape[0] <= L.GROUP_MAX_TYPES:
+            raise ValueError(f"{lab.shape[0]} groupings: 1 .. {L.GROUP_MAX_TYPES} a call")
+        return lab
+
+    def _cross_within(self, queries, max_dist: float, rows, cols, flags: int, capacity):
+        r0, r1 = rows or (0, len(queries))
+        c0, c1 = cols or (0, len(self))
+        nr = max(r1 - r0, 0)
+        rowptr = np.zeros(nr + 1, dtype=np.int64)
+        total = C.c_int64(0)
+        cap = int(capacity) if capacity is not None else max(nr, 1) * self.WITHIN_GUESS_PER_ROW
+        while True:
+            # non-empty buffers behind empty results: the library is never handed a null output
+            col = np.zeros(max(cap, 1), dtype=np.int64)
+            d = np.zeros(max(cap, 1), dtype=np.float64)
+            L.check(L.lib.gdist_cross_within(self.ctx.h, queries.h, self.h, r0, r1, c0, c1, flags, float(max_dist), cap,
+                                             L.ptr(rowptr, C.c_int64), L.ptr(col, C.c_int64), L.ptr(d, C.c_double),
+                                             C.byref(total)))
+            if capacity is not None or total.value <= cap:
+                m = min(total.value, cap)
+                return rowptr, col[:m], d[:m]
+            cap = total.value
+
+    def _cross_group_stats(self, queries, qlabels, slabels, rows, cols, flags: int) -> GroupStats:
+        ql = self._cross_labels(qlabels, len(queries), "qlabels")
+        sl = self._cross_labels(slabels, len(self), "slabels")
+        if ql.shape[0] != sl.shape[0]:
+            raise ValueError(f"{ql.shape[0]} query groupings but {sl.shape[0]} subject groupings")
+        T = ql.shape[0]
+        r0, r1 = rows or (0, len(queries))
+        c0, c1 = cols or (0, len(self))
+        sides, bad = (L.GroupSide * (2 * T))(), (C.c_int64 * T)()
+        qb = ql if ql.size else np.zeros(1, dtype=np.int32)
+        sb = sl if sl.size else np.zeros(1, dtype=np.int32)
+        L.check(L.lib.gdist_cross_group_stats(self.ctx.h, queries.h, self.h, r0, r1, c0, c1,
+                                              flags, T, L.ptr(qb, C.c_int32),
+                                              L.ptr(sb, C.c_int32), C.addressof(sides), bad))
+        return GroupStats(sides, bad)
+
+    def _cross_histogram(self, queries, edges, qlabels, slabels, rows, cols, flags: int) -> Histogram:
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        if not 1 <= len(e) <= L.HIST_MAX_EDGES:
+            raise ValueError(f"{len(e)} edges: 1 .. {L.HIST_MAX_EDGES} a call")
+        if (qlabels is None) != (slabels is None):
+            raise ValueError("qlabels and slabels come together")
+        T, qb, sb = 0, None, None
+        if qlabels is not None:
+            ql = self._cross_labels(qlabels, len(queries), "qlabels")
+            sl = self._cross_labels(slabels, len(self), "slabels")
+            if ql.shape[0] != sl.shape[0]:
+                raise ValueError(f"{ql.shape[0]} query groupings but {sl.shape[0]} subject groupings")
+            T = ql.shape[0]
+            qb = ql if ql.size else np.zeros(1, dtype=np.int32)
+            sb = sl if sl.size else np.zeros(1, dtype=np.int32)
+        r0, r1 = rows or (0, len(queries))
+        c0, c1 = cols or (0, len(self))
+        S = 2 * T if T else 1
+        counts = np.zeros((S, len(e) + 1), dtype=np.int64)
+        nans = np.zeros(S, dtype=np.int64)
+        bad = np.zeros(max(T, 1), dtype=np.int64)
+        L.check(L.lib.gdist_cross_histogram(self.ctx.h, queries.h, self.h, r0, r1, c0, c1,
+                                            flags, len(e), L.ptr(e, C.c_double), T,
+                                            L.ptr(qb, C.c_int32) if T else None, L.ptr(sb, C.c_int32) if T else None,
+                                            L.ptr(counts, C.c_int64), L.ptr(nans, C.c_int64),
+                                            L.ptr(bad, C.c_int64) if T else None))
+        return Histogram(e, counts, nans, bad[:T])
+
     def getClosest(self, n: int, max_dist: float, **kw) -> list[list[tuple[int, float]]]:
         """getClosest(kmers, n, maxDist) for every row of closest(n, max_dist, **kw)
         (MashProcessor.java:150, FindProcessor.java:110), exhaustively: per query
@@ -980,15 +1083,7 @@ class KmerSets(_Handle):
         collection is only read (its segment index is built when absent) and
         nothing is packed again: bit for bit the rectangle matrix(method=
         METHOD_SORTED) gives for self.concat(queries). flags: EMPTY_NAN or 0."""
-        r0, r1 = rows or (0, len(queries))
-        c0, c1 = cols or (0, len(self))
-        nr, nc = max(r1 - r0, 0), max(c1 - c0, 0)
-        I = np.full((nr, nc), -1, dtype=np.int32) if want_I else None
-        D = np.full((nr, nc), np.nan, dtype=np.float64) if want_D else None
-        L.check(L.lib.gdist_cross_matrix(self.ctx.h, queries.h, self.h, r0, r1, c0, c1, flags,
-                                         L.ptr(I, C.c_int32) if want_I else None,
-                                         L.ptr(D, C.c_double) if want_D else None, max(nc, 1)))
-        return I, D
+        return self._cross_matrix(queries, rows, cols, flags, want_I, want_D)
 
     def cross_closest(self, queries: "KmerSets", n: int, max_dist: float, rows: tuple[int, int] | None = None,
                       cols: tuple[int, int] | None = None, flags: int = 0):
@@ -999,31 +1094,7 @@ class KmerSets(_Handle):
         int64, d[nr, n] float64, count[nr] int32) laid out as closest() lays
         them out; d is cross_matrix()'s D bit for bit. This collection is only
         read and nothing is packed again."""
-        r0, r1 = rows or (0, len(queries))
-        c0, c1 = cols or (0, len(self))
-        nr = max(r1 - r0, 0)
-        idx = np.full((nr, max(n, 0)), -1, dtype=np.int64)
-        d = np.ones((nr, max(n, 0)), dtype=np.float64)
-        cnt = np.zeros(nr, dtype=np.int32)
-        # non-empty buffers behind empty results: the library is never handed a null output
-        bi = idx if idx.size else np.zeros(1, dtype=np.int64)
-        bd = d if d.size else np.zeros(1, dtype=np.float64)
-        bc = cnt if cnt.size else np.zeros(1, dtype=np.int32)
-        L.check(L.lib.gdist_cross_closest(self.ctx.h, queries.h, self.h, r0, r1, c0, c1, flags, int(n),
-                                          float(max_dist), L.ptr(bi, C.c_int64), L.ptr(bd, C.c_double),
-                                          L.ptr(bc, C.c_int32)))
-        return idx, d, cnt
-
-    @staticmethod
-    def _cross_labels(labels, n: int, what: str) -> np.ndarray:
-        lab = np.ascontiguousarray(labels, dtype=np.int32)
-        if lab.ndim == 1:
-            lab = lab[None, :]
-        if lab.ndim != 2 or lab.shape[1] != n:
-            raise ValueError(f"{what} must be [T, {n}] or [{n}], not {list(lab.shape)}")
-        if not 1 <= lab.shape[0] <= L.GROUP_MAX_TYPES:
-            raise ValueError(f"{lab.shape[0]} groupings: 1 .. {L.GROUP_MAX_TYPES} a call")
-        return lab
+        return self._cross_closest(queries, n, max_dist, rows, cols, flags)
 
     def cross_within(self, queries: "KmerSets", max_dist: float, rows: tuple[int, int] | None = None,
                      cols: tuple[int, int] | None = None, empty_nan: bool = False, capacity: int | None = None):
@@ -1036,24 +1107,7 @@ class KmerSets(_Handle):
         when the total exceeds it, as within()); a number: at most that many
         entries, rowptr still the full counts. d is cross_matrix()'s D bit for
         bit. This collection is only read and nothing is packed again."""
-        r0, r1 = rows or (0, len(queries))
-        c0, c1 = cols or (0, len(self))
-        nr = max(r1 - r0, 0)
-        fl = L.EMPTY_NAN if empty_nan else 0
-        rowptr = np.zeros(nr + 1, dtype=np.int64)
-        total = C.c_int64(0)
-        cap = int(capacity) if capacity is not None else max(nr, 1) * self.WITHIN_GUESS_PER_ROW
-        while True:
-            # non-empty buffers behind empty results: the library is never handed a null output
-            col = np.zeros(max(cap, 1), dtype=np.int64)
-            d = np.zeros(max(cap, 1), dtype=np.float64)
-            L.check(L.lib.gdist_cross_within(self.ctx.h, queries.h, self.h, r0, r1, c0, c1, fl, float(max_dist), cap,
-                                             L.ptr(rowptr, C.c_int64), L.ptr(col, C.c_int64), L.ptr(d, C.c_double),
-                                             C.byref(total)))
-            if capacity is not None or total.value <= cap:
-                m = min(total.value, cap)
-                return rowptr, col[:m], d[:m]
-            cap = total.value
+        return self._cross_within(queries, max_dist, rows, cols, L.EMPTY_NAN if empty_nan else 0, capacity)
 
     def cross_group_stats(self, queries: "KmerSets", qlabels, slabels, rows: tuple[int, int] | None = None,
                           cols: tuple[int, int] | None = None, empty_nan: bool = False) -> GroupStats:
@@ -1063,20 +1117,7 @@ class KmerSets(_Handle):
         1-d for one grouping), the group of every set (< 0: none, the pair is
         counted as bad). Every cell of the rectangle counts. The result merges
         with any other GroupStats; this collection is only read."""
-        ql = self._cross_labels(qlabels, len(queries), "qlabels")
-        sl = self._cross_labels(slabels, len(self), "slabels")
-        if ql.shape[0] != sl.shape[0]:
-            raise ValueError(f"{ql.shape[0]} query groupings but {sl.shape[0]} subject groupings")
-        T = ql.shape[0]
-        r0, r1 = rows or (0, len(queries))
-        c0, c1 = cols or (0, len(self))
-        sides, bad = (L.GroupSide * (2 * T))(), (C.c_int64 * T)()
-        qb = ql if ql.size else np.zeros(1, dtype=np.int32)
-        sb = sl if sl.size else np.zeros(1, dtype=np.int32)
-        L.check(L.lib.gdist_cross_group_stats(self.ctx.h, queries.h, self.h, r0, r1, c0, c1,
-                                              L.EMPTY_NAN if empty_nan else 0, T, L.ptr(qb, C.c_int32),
-                                              L.ptr(sb, C.c_int32), C.addressof(sides), bad))
-        return GroupStats(sides, bad)
+        return self._cross_group_stats(queries, qlabels, slabels, rows, cols, L.EMPTY_NAN if empty_nan else 0)
 
     def cross_histogram(self, queries: "KmerSets", edges, qlabels=None, slabels=None,
                         rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,
@@ -1087,32 +1128,8 @@ class KmerSets(_Handle):
         qlabels / slabels (as cross_group_stats) an in-group and an out-group
         series per grouping. Every cell of the rectangle counts; histograms of
         disjoint rectangles add. This collection is only read."""
-        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
-        if not 1 <= len(e) <= L.HIST_MAX_EDGES:
-            raise ValueError(f"{len(e)} edges: 1 .. {L.HIST_MAX_EDGES} a call")
-        if (qlabels is None) != (slabels is None):
-            raise ValueError("qlabels and slabels come together")
-        T, qb, sb = 0, None, None
-        if qlabels is not None:
-            ql = self._cross_labels(qlabels, len(queries), "qlabels")
-            sl = self._cross_labels(slabels, len(self), "slabels")
-            if ql.shape[0] != sl.shape[0]:
-                raise ValueError(f"{ql.shape[0]} query groupings but {sl.shape[0]} subject groupings")
-            T = ql.shape[0]
-            qb = ql if ql.size else np.zeros(1, dtype=np.int32)
-            sb = sl if sl.size else np.zeros(1, dtype=np.int32)
-        r0, r1 = rows or (0, len(queries))
-        c0, c1 = cols or (0, len(self))
-        S = 2 * T if T else 1
-        counts = np.zeros((S, len(e) + 1), dtype=np.int64)
-        nans = np.zeros(S, dtype=np.int64)
-        bad = np.zeros(max(T, 1), dtype=np.int64)
-        L.check(L.lib.gdist_cross_histogram(self.ctx.h, queries.h, self.h, r0, r1, c0, c1,
-                                            L.EMPTY_NAN if empty_nan else 0, len(e), L.ptr(e, C.c_double), T,
-                                            L.ptr(qb, C.c_int32) if T else None, L.ptr(sb, C.c_int32) if T else None,
-                                            L.ptr(counts, C.c_int64), L.ptr(nans, C.c_int64),
-                                            L.ptr(bad, C.c_int64) if T else None))
-        return Histogram(e, counts, nans, bad[:T])
+        return self._cross_histogram(queries, edges, qlabels, slabels, rows, cols,
+                                     L.EMPTY_NAN if empty_nan else 0)
 
     def row_query(self, q: int, cols: Iterable[int], mode: int = L.QUERY_ALL, t: float = 1.0):
         cl = np.ascontiguousarray(np.fromiter(cols, dtype=np.int64))
@@ -1244,6 +1261,49 @@ class SketchSets(_Handle):
         """Exact order statistics of the sketch distances (flags: SKETCH_JACCARD,
         EMPTY_NAN; method is ignored): as KmerSets.quantiles."""
         return self._quantiles(q, rows, cols, upper, L.METHOD_AUTO, flags)
+
+    # Query sketches against this resident sketch database (the reference's
+    # find / mash: one getClosest per incoming genome). `queries` is a
+    # SketchSets of the same width and kmer spec; this collection is only
+    # read, nothing is built on it and nothing is copied. Each call gives, bit
+    # for bit, what its one-collection twin gives on self.concat(queries) for
+    # rows len(self) + rows x cols with keep_self. flags: SKETCH_JACCARD,
+    # EMPTY_NAN (empty_nan=True adds the latter).
+    def cross_matrix(self, queries: "SketchSets", rows: tuple[int, int] | None = None,
+                     cols: tuple[int, int] | None = None, flags: int = 0, want_I: bool = True,
+                     want_D: bool = True):
+        """Common counts (matrix()'s `common`) and sketch distances of `queries`
+        (rows) against this collection (cols) (gdist_cross_matrix)."""
+        return self._cross_matrix(queries, rows, cols, flags, want_I, want_D)
+
+    def cross_closest(self, queries: "SketchSets", n: int, max_dist: float, rows: tuple[int, int] | None = None,
+                      cols: tuple[int, int] | None = None, flags: int = 0):
+        """Exact nearest neighbours of `queries` among this collection by sketch
+        distance (gdist_cross_closest): (idx, d, count) as KmerSets.cross_closest."""
+        return self._cross_closest(queries, n, max_dist, rows, cols, flags)
+
+    def cross_within(self, queries: "SketchSets", max_dist: float, rows: tuple[int, int] | None = None,
+                     cols: tuple[int, int] | None = None, empty_nan: bool = False, capacity: int | None = None,
+                     flags: int = 0):
+        """Every (query, resident sketch) pair within a sketch distance
+        (gdist_cross_within): CSR as KmerSets.cross_within."""
+        return self._cross_within(queries, max_dist, rows, cols, flags | (L.EMPTY_NAN if empty_nan else 0), capacity)
+
+    def cross_group_stats(self, queries: "SketchSets", qlabels, slabels, rows: tuple[int, int] | None = None,
+                          cols: tuple[int, int] | None = None, empty_nan: bool = False,
+                          flags: int = 0) -> GroupStats:
+        """In-group / out-group summary of the sketch distances of `queries`
+        against this collection (gdist_cross_group_stats): as KmerSets.cross_group_stats."""
+        return self._cross_group_stats(queries, qlabels, slabels, rows, cols,
+                                       flags | (L.EMPTY_NAN if empty_nan else 0))
+
+    def cross_histogram(self, queries: "SketchSets", edges, qlabels=None, slabels=None,
+                        rows: tuple[int, int] | None = None, cols: tuple[int, int] | None = None,
+                        empty_nan: bool = False, flags: int = 0) -> Histogram:
+        """How the sketch distances of `queries` against this collection are
+        distributed (gdist_cross_histogram): as KmerSets.cross_histogram."""
+        return self._cross_histogram(queries, edges, qlabels, slabels, rows, cols,
+                                     flags | (L.EMPTY_NAN if empty_nan else 0))
 
     def matrix_device(self, d_common: int | None, d_D: int | None, ld: int, rows, cols, upper=False, flags=0):
         fl = flags | L.OUT_DEVICE | (L.UPPER_TRIANGLE if upper else 0)

@@ -27,7 +27,7 @@ import numpy as np
 from . import _lib as L
 from .fasta import Sequence as FastaRecord
 from .javafmt import java_double, java_format_f
-from .kmers import Context, KmerSets, KmerType
+from .kmers import Context, KmerSets, KmerType, SketchSets
 
 
 class ParseFailureException(ValueError):
@@ -406,8 +406,9 @@ def closest_genomes(queries: Sequence[Genome], subjects: Sequence[Genome], out: 
     return nq, found, none
 
 
-def find_genomes(db: KmerSets, subjects: Sequence[Genome], queries: Iterable[Genome], out: TextIO,
-                 neighbors: int = 10, max_dist: float = 0.9, batch: int = 64) -> tuple[int, int]:
+def find_genomes(db: "KmerSets | SketchSets", subjects: Sequence[Genome], queries: Iterable[Genome], out: TextIO,
+                 neighbors: int = 10, max_dist: float = 0.9, batch: int = 64, kmer_size: int | None = None,
+                 kmer_type: KmerType = KmerType.DNA, flags: int = 0) -> tuple[int, int]:
     """The `find` table over a resident database: `db` holds the kmer sets of
     `subjects` (set j is subjects[j]) and stays on the device as it is, as the
     reference loads its genome database once and then answers one getClosest
@@ -417,7 +418,13 @@ def find_genomes(db: KmerSets, subjects: Sequence[Genome], queries: Iterable[Gen
     the LSH buckets), nearest first, ties by subject order. The neighbour's id
     and name are one field with a tab inside, as the database returns them.
     Returns (neighbours found, searches with none), the counters of the
-    reference's closing log line."""
+    reference's closing log line.
+
+    `db` may be a SketchSets (the reference's MinHash database): the queries
+    are then packed with kmer_size, kmer_type and flags (the spec the
+    database's sketches were made from; read for a sketch database only),
+    sketched to the database's width and go through SketchSets.cross_closest,
+    SKETCH_JACCARD and EMPTY_NAN of `flags` passed on to it."""
     # the database loaded once, one getClosest per genome: FindProcessor.java:94-110
     # defaults (10 neighbours, 0.9): FindProcessor.java:72-73
     # the header: FindProcessor.java:100
@@ -426,15 +433,33 @@ def find_genomes(db: KmerSets, subjects: Sequence[Genome], queries: Iterable[Gen
         raise ValueError(f"the database holds {len(db)} sets but {len(subjects)} subjects were named")
     if batch < 1:
         raise ValueError("batch must be at least 1")
+    sketched = isinstance(db, SketchSets)
+    if sketched and kmer_size is None:
+        raise ValueError("a sketch database needs the kmer_size its sketches were made with")
     found = fail = 0
+
+    def closest_of(group):
+        texts = [g.kmer_text() for g in group]
+        if not sketched:
+            qs = db.pack_like(texts)
+            try:
+                return db.cross_closest(qs, neighbors, max_dist)
+            finally:
+                qs.free()
+        pack_flags = flags & ~(L.SKETCH_JACCARD | L.EMPTY_NAN)
+        ks = KmerSets.from_sequences(texts, kmer_size, kmer_type, pack_flags, db.ctx)
+        try:
+            qs = ks.sketches(db.info()[1])
+        finally:
+            ks.free()
+        try:
+            return db.cross_closest(qs, neighbors, max_dist, flags=flags & (L.SKETCH_JACCARD | L.EMPTY_NAN))
+        finally:
+            qs.free()
 
     def flush(group):
         nonlocal found, fail
-        qs = db.pack_like([g.kmer_text() for g in group])
-        try:
-            idx, d, cnt = db.cross_closest(qs, neighbors, max_dist)
-        finally:
-            qs.free()
+        idx, d, cnt = closest_of(group)
         for a, q in enumerate(group):
             # no neighbour counts as a failure: FindProcessor.java:111
             if cnt[a] == 0:

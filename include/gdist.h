@@ -559,8 +559,8 @@ int  gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, in
 /* ---- new query sets against a resident collection ---------------------- */
 /* The reference loads its genome database once and answers one
  * getClosest(kmers, n, maxDist) per incoming genome (FindProcessor.java:94-110,
- * MashProcessor.java:150). `subjects` is that database: a kmer-set collection
- * that stays as it is. `queries` is another collection of the same context and
+ * MashProcessor.java:150). `subjects` is that database: a collection of kmer
+ * sets (or of sketches, below) that stays as it is. `queries` is another collection of the same context and
  * kmer spec (what gdist_sets_concat would accept; GDIST_NO_CASE_FOLD may
  * differ). Rows are query sets [q0, q1), columns subject sets [c0, c1).
  *
@@ -584,9 +584,30 @@ int  gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, in
  *
  * Both run the sorted join over work units (query row, <= 64 consecutive
  * subject columns, a range of the subjects' segment index), so one query
- * against many subjects still fills the device; kmer sets only (the pruned
- * dictionary of the subjects cannot answer for kmers that only a query and
- * one subject share; sketches: gdist_lsh_closest).
+ * against many subjects still fills the device (the pruned dictionary of the
+ * subjects cannot answer for kmers that only a query and one subject share).
+ *
+ * Sketches. Every cross call also takes two GDIST_SKETCH collections of one
+ * context, width and kmer spec (what gdist_sets_concat accepts): the
+ * reference's MinHash database and the sketches of incoming genomes. One
+ * sketch collection and one of kmer sets is EINVAL. For a sketch pair
+ *  - flags may hold GDIST_SKETCH_JACCARD beside GDIST_EMPTY_NAN, with the
+ *    meaning they have in gdist_sketch_matrix;
+ *  - gdist_cross_matrix's I_out is the common count (gdist_sketch_matrix's
+ *    common_out) and D_out the sketch distance;
+ *  - each call returns, bit for bit, what its twin (gdist_sketch_matrix,
+ *    gdist_closest, gdist_within, gdist_group_stats, gdist_histogram) returns
+ *    on gdist_sets_concat(subjects, queries) for rows [ns+q0, ns+q1) x cols
+ *    [c0, c1) with the same flags (plus GDIST_CLOSEST_KEEP_SELF for closest
+ *    and within) and the labels slabels[t] followed by qlabels[t]; every other
+ *    rule below carries over;
+ *  - a wave merges a (query, subject) pair in 64 segments, a workgroup holds
+ *    a run of subjects on chip for every query row of the step: one query
+ *    against a million subjects fills the device, the subjects are read once
+ *    a step and never copied. Nothing is built or kept on either collection
+ *    (there is no segment index here); both need their signatures.
+ * The exact list this gives is the yardstick of gdist_lsh_closest, which looks
+ * at the LSH buckets only.
  *
  * The subjects are read only: bitsets, tiers, launch plans, captured graphs,
  * codes and the number of sets are as before the call. The one thing a cross
@@ -598,11 +619,13 @@ int  gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, in
  * An empty row or column range: GDIST_OK; the matrix outputs are untouched,
  * the closest counts are 0 with slots -1 / 1.0 (n == 0 likewise). EINVAL,
  * decided before any work with every output untouched: a null handle,
- * collections of another context or of different contexts, a GDIST_SKETCH
- * collection, kmer specs gdist_sets_concat would refuse, a collection without
+ * collections of another context or of different contexts, one GDIST_SKETCH
+ * collection with one of kmer sets, kmer specs (or sketch widths)
+ * gdist_sets_concat would refuse, a collection without
  * codes (released, or from gdist_sets_allgather_bitsets), a range outside its
  * collection, ld < c1 - c0, both matrix outputs NULL on a non-empty
- * rectangle, any flag but GDIST_EMPTY_NAN, n < 0 or n > GDIST_CLOSEST_MAX_N,
+ * rectangle, any flag but GDIST_EMPTY_NAN (sketches: and
+ * GDIST_SKETCH_JACCARD), n < 0 or n > GDIST_CLOSEST_MAX_N,
  * NaN max_dist, NULL closest outputs with a non-empty row range, subjects of
  * 2^32 - 1 sets or more. */
 int  gdist_cross_matrix(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects,
@@ -620,7 +643,7 @@ int  gdist_cross_closest(gdist_ctx* ctx, const gdist_sets* queries, const gdist_
  * read-only rule for the subjects as the two calls above. Each takes its
  * twin's arguments with `sets` replaced by `queries, subjects` and without
  * `method`; column indices in the outputs (col_out) are subject indices. The
- * only flag is GDIST_EMPTY_NAN: no column is "self" and there is no
+ * only flag is GDIST_EMPTY_NAN (a sketch pair: and GDIST_SKETCH_JACCARD): no column is "self" and there is no
  * GDIST_UPPER_TRIANGLE, so every cell of the rectangle counts, and the same
  * handle passed for both collections behaves as GDIST_CLOSEST_KEEP_SELF
  * without GDIST_UPPER_TRIANGLE. Labels come per side: qlabels[t * nq + i] the
@@ -676,7 +699,10 @@ int  gdist_cross_histogram(gdist_ctx* ctx, const gdist_sets* queries, const gdis
  * (gdist_cross_closest: the select; gdist_cross_matrix: the distance
  * epilogue, 0 without D_out; gdist_cross_within: count, scan and write;
  * gdist_cross_group_stats: the reduce; gdist_cross_histogram: the histogram
- * kernel), and the work units launched */
+ * kernel), and the work units launched. A sketch pair: join_ms is the merge
+ * kernel, select_ms the same consumers (0 for gdist_cross_matrix: D comes from
+ * the merge itself), units the (query, subject) pairs merged,
+ * (q1 - q0) (c1 - c0) */
 int  gdist_ctx_cross_info(gdist_ctx* ctx, double* join_ms, double* select_ms, int64_t* units);
 
 /* ---- distribution of the distances ------------------------------------- */
