@@ -1363,6 +1363,37 @@ int gdist_sketch_matrix(gdist_ctx* ctx, const gdist_sets* sk, int64_t r0, int64_
     });
 }
 
+int gdist_sketch_pairs(gdist_ctx* ctx, const gdist_sets* a, const gdist_sets* b, int64_t npairs, const int64_t* rows,
+                       const int64_t* cols, unsigned flags, int32_t* common_out, double* D_out) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_sets(a);
+        check_sets(b);
+        GD_REQUIRE(a->ctx == ctx && b->ctx == ctx, "sketches belong to another context");
+        GD_REQUIRE(a->kind == GDIST_SKETCH && b->kind == GDIST_SKETCH,
+                   "sketch pair lists run on two GDIST_SKETCH collections (kmer sets: gdist_pairs)");
+        check_same_spec(a, b);
+        check_codes(a);
+        check_codes(b);
+        GD_REQUIRE(npairs >= 0 && npairs < (int64_t(1) << 31), "npairs outside 0 .. 2^31 - 1");
+        GD_REQUIRE(!(flags & ~(GDIST_EMPTY_NAN | GDIST_SKETCH_JACCARD)),
+                   "gdist_sketch_pairs takes no flag but GDIST_EMPTY_NAN and GDIST_SKETCH_JACCARD");
+        GD_REQUIRE(npairs == 0 || (rows && cols), "null rows or cols");
+        GD_REQUIRE(npairs == 0 || common_out || D_out, "both outputs null");
+        for (int64_t p = 0; p < npairs; p++) {
+            GD_REQUIRE(rows[p] >= 0 && rows[p] < a->nsets, "row index outside the first collection");
+            GD_REQUIRE(cols[p] >= 0 && cols[p] < b->nsets, "column index outside the second collection");
+        }
+        ctx->pairs_kernel_ms = -1.0;
+        ctx->pairs_groups = ctx->pairs_units = 0;
+        if (npairs == 0) return;
+        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
+        ctx->last = Timing{};
+        gdist::sketch_pairs(ctx, a, b, flags, npairs, rows, cols, common_out, D_out);
+    });
+}
+
 // ---------------------------------------------------------------------------
 int gdist_lsh_build(gdist_ctx* ctx, const gdist_sets* sketches, int stages, int buckets, uint64_t seed,
                     gdist_lsh** out) {

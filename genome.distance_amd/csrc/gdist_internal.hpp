@@ -350,7 +350,7 @@ struct gdist_ctx {
     double within_matrix_ms = -1.0, within_select_ms = -1.0;
     // the same for the last gdist_histogram call: matrix kernels, histogram kernel
     double hist_matrix_ms = -1.0, hist_reduce_ms = -1.0;
-    // the last gdist_pairs call: its kernels' time (option time_kernels = 1, else -1),
+    // the last gdist_pairs or gdist_sketch_pairs call: its kernels' time (option time_kernels = 1, else -1),
     // the distinct-row groups of its list and the work units launched for them
     double pairs_kernel_ms = -1.0;
     int64_t pairs_groups = 0, pairs_units = 0;
@@ -932,6 +932,12 @@ void hist_count(gdist_ctx* ctx, WalkSource& src, int64_t r0, int64_t r1, int64_t
 // rows / cols / I_out / D_out: host, n entries, either output may be null
 void pairs(gdist_ctx* ctx, const gdist_sets* s, int method, unsigned flags, int64_t n, const int64_t* rows,
            const int64_t* cols, int32_t* I_out, double* D_out);
+
+// sketch_pairs.hip — the sketch distances of a pair list (gdist_sketch_pairs)
+// every argument checked by the caller, n > 0; rows index a, cols index b;
+// rows / cols / common_out / D_out: host, n entries, either output may be null
+void sketch_pairs(gdist_ctx* ctx, const gdist_sets* a, const gdist_sets* b, unsigned flags, int64_t n,
+                  const int64_t* rows, const int64_t* cols, int32_t* common_out, double* D_out);
 
 // lsh.hip
 void lsh_build(gdist_ctx* ctx, const gdist_sets* sk, int stages, int buckets, uint64_t seed, gdist_lsh* L);

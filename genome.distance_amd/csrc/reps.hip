@@ -106,6 +106,7 @@ void greedy_reps(gdist_ctx* ctx, gdist_sets* s, int method, double t, const int6
     GD_HIP(hipMemsetAsync(drep.p, 0, n * 4, st));
     std::vector<int32_t> cov(B);
     std::vector<double> tile((size_t)B * B);
+    DevBuf dtile(split ? 8 : (size_t)B * B * 8 + 8, st);   // the in-block tile, dense
     DevBuf gcov(split ? (size_t)R * B * 4 + 4 : 4, st);
     std::vector<int32_t> hcov(split ? (size_t)R * B : 1);
     int64_t count = 0;
@@ -120,11 +121,14 @@ void greedy_reps(gdist_ctx* ctx, gdist_sets* s, int method, double t, const int6
                 GD_HIP(hipGetLastError());
                 d2h(cov.data(), dcov.p, nb * 4, st);
             }
-            // the in-block tile D[b0..b1) x [b0..b1)
-            GD_HIP(hipStreamSynchronize(st));
-            GD_HIP(hipMemcpy2DAsync(tile.data(), nb * 8, dD.as<double>() + b0, b1 * 8, nb * 8, nb,
-                                    hipMemcpyDeviceToHost, st));
-            GD_HIP(hipStreamSynchronize(st));
+            // the in-block tile D[b0..b1) x [b0..b1): gathered on the device, then
+            // one linear download through d2h as every other host transfer (a
+            // strided async copy straight into the pageable vector has returned
+            // "illegal memory access" from the copy call itself, after the
+            // stream's kernels had all completed)
+            GD_HIP(hipMemcpy2DAsync(dtile.p, nb * 8, dD.as<double>() + b0, b1 * 8, nb * 8, nb,
+                                    hipMemcpyDeviceToDevice, st));
+            d2h(tile.data(), dtile.p, (size_t)nb * nb * 8, st);
         } else {
             distance_rows(ctx, s, method, b0, b1, b0, b1, dI.as<int32_t>(), dD.as<double>(), nb);
             GD_HIP(hipStreamSynchronize(st));

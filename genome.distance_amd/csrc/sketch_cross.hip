@@ -7,7 +7,8 @@
 // ~1000. sketch.hip's kernels give a lane a pair (about 2 s dependent steps at
 // data-dependent addresses); one query row leaves them 1 lane in 32. Here a
 // WAVE takes a pair and its 64 lanes merge 64 segments of it
-// (sketch_cross_merge.hpp): ~2 s / 64 steps and a binary search a lane.
+// (skx_pair_merge, sketch_wave_merge.hpp): ~2 s / 64 steps and a binary search
+// a lane.
 //
 // sketch_cross_kernel: a workgroup of 16 waves owns a run of `st` consecutive
 // subjects of the step's columns and meets them with EVERY query row of the
@@ -24,7 +25,7 @@
 // Lane 0 stores the pair's common count and / or distance: plain stores into
 // the step's block, row stride nk.
 #include "gdist_internal.hpp"
-#include "sketch_cross_merge.hpp"
+#include "sketch_wave_merge.hpp"
 
 namespace gdist {
 namespace {
@@ -33,50 +34,6 @@ constexpr int kNT = 1024, kNW = kNT / 64;  // threads, waves of a workgroup
 constexpr int kQT = 4;                     // query rows staged at a time
 constexpr int kMinRun = 4, kMaxRun = 64;   // subjects a workgroup holds
 constexpr int kLdsDwords = 16000;          // 62.5 KiB of signatures: two workgroups a CU
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ int wave_scan(int v, int lane) {   // inclusive
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(v, o, 64);
-        if (lane >= o) v += up;
-    }
-    return v;
-}
-
-// one pair by the 64 lanes of a wave; every lane returns the pair's result
-__device__ __forceinline__ void pair_merge(const int32_t* Q, int nq, const int32_t* S, int ns, int width,
-                                           int jaccard, int empty_nan, int lane, int* common_out, double* d_out) {
-    const bool qa = nq >= ns;
-    const int32_t* A = qa ? Q : S;
-    const int32_t* B = qa ? S : Q;
-    const int na = qa ? nq : ns, nb = qa ? ns : nq;
-    const int ca = skx_chunk(na);
-    int a0, a1;
-    skx_a_range(na, ca, lane, &a0, &a1);
-    const int b0 = skx_b_begin(A, na, B, nb, ca, lane);
-    int b1 = __shfl_down(b0, 1, 64);
-    if (lane == kSkxLanes - 1) b1 = nb;
-    uint64_t mask;
-    const int c = skx_merge(A, a0, a1, B, b0, b1, &mask);
-    int common, taken;
-    if (jaccard) {
-        common = wave_sum(c);
-        taken = na + nb - common;
-    } else {
-        const int uni = (a1 - a0) + (b1 - b0) - c;
-        const int incl = wave_scan(uni, lane);
-        taken = skx_taken(__shfl(incl, kSkxLanes - 1, 64), width, 0);
-        common = wave_sum(skx_lane_common(A, a0, a1, B, b0, b1, incl - uni, uni, c, mask, taken));
-    }
-    *common_out = common;
-    *d_out = skx_distance(common, taken, na, nb, jaccard, empty_nan);
-}
 
 // Sets [first, first + n) of a CSR collection into LDS as they lie: their
 // hashes sig[off[first] .. off[first + n]) to dst (at most cap dwords), and
@@ -148,7 +105,7 @@ __global__ __launch_bounds__(kNT) void sketch_cross_kernel(
             }
             int common;
             double d;
-            pair_merge(Q, lq, S, ls, width, jaccard, empty_nan, lane, &common, &d);
+            skx_pair_merge(Q, lq, S, ls, width, jaccard, empty_nan, lane, &common, &d);
             if (lane == 0) {
                 const int64_t o = (t0 + r) * nk + j0 + s;
                 if (common_out) common_out[o] = common;

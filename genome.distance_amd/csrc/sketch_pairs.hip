@@ -1,0 +1,257 @@
+// sketch_pairs.hip — the sketch distances of an arbitrary (row, column) pair
+// list in one call (gdist_sketch_pairs).
+//
+// The lists of the reference that name their pairs: the methods table
+// (MethodTableProcessor.java:258-276), one genome against a column list, and
+// the chosen pairs the width comparison sets beside the exact distance
+// (WidthProcessor.java:183-192). The rectangle kernels do not fit: 10^5
+// scattered pairs among 50,000 sketches are 4e-5 of their bounding rectangle.
+//
+// Plan (on the device, as pairs.hip: one upload, no host round trip): the pair
+// positions are sorted by row (sort_pairs_u64_i32, stable: positions ascend
+// within a row); a run of equal row is a group, cut into units of at most
+// kSkpUnitPairs consecutive pairs (sketch_pairs_plan.hpp). A signature is at
+// most `width` hashes, so there is no code budget and a pair is never split.
+// skp_plan_kernel marks the unit heads and counts the groups, a scan places
+// the units, skp_units_kernel writes them; the merge kernel reads their number
+// from device memory and strides over them.
+//
+// sketch_pairs_kernel: a workgroup of 16 waves takes units in a grid-stride
+// loop, up to kRows consecutive ones a step: a scattered list's units hold
+// ~20 pairs, and 16 waves on one such unit leave the second round a quarter
+// full; the pairs of a step's units go to the waves in turn as one run. A
+// short list is not batched (every workgroup keeps kStepsPerWg steps).
+//   LDS variant: a unit's row signature is staged once (one flat coalesced
+//   copy by the whole workgroup); each wave then copies its pair's column
+//   signature into its own LDS slice (64 lanes, coalesced, at most `width`
+//   dwords) and merges the two with the wave-per-pair merge of the cross kernel
+//   (skx_pair_merge). The merge is a chain of dependent reads at data-dependent
+//   addresses: ~2 width / 64 short steps from LDS, an HBM / L2 latency each
+//   from global memory; the gather stays one wide load a signature. Rows and
+//   slices are sw = width | 1 dwords apart, so they start on different banks.
+//   (1 + 16) sw dwords a unit, 68 KB at width 1000; with kRows = 4 rows 80 KB,
+//   still two workgroups in a CU's 160 KiB: what hides the merge latency is
+//   waves. Fewer rows a step where only fewer fit (widths 1,024 .. 1,203).
+//   Global variant (a row and the slices past kLdsBytes): the same walk,
+//   searching and merging straight from global memory. Width 20,000 runs here.
+// Lane 0 stores the pair's common count and / or distance at the pair's
+// original position: every position is in exactly one unit, so nothing is
+// zeroed and nothing at or past npairs is touched.
+#include <cstring>
+
+#include "gdist_internal.hpp"
+#include "sketch_pairs_plan.hpp"
+#include "sketch_wave_merge.hpp"
+
+namespace gdist {
+namespace {
+
+constexpr int kNT = 1024, kNW = kNT / 64;   // threads, waves of a workgroup
+constexpr int kLdsBytes = 80 * 1024;        // a workgroup's signatures: two workgroups in a CU's 160 KiB
+constexpr int kWgPerCu = 2;                 // 16-wave workgroups a CU holds
+constexpr int kRows = 4;                    // units a workgroup holds at a time, at most
+constexpr int kStepsPerWg = 4;              // steps a workgroup keeps before units are batched
+
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ void skp_keys_kernel(const int64_t* __restrict__ rows, int64_t n, uint64_t* __restrict__ keys,
+                                int32_t* __restrict__ vals) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    keys[p] = (uint64_t)rows[p];
+    vals[p] = (int32_t)p;
+}
+
+// counts[0] += the group heads; uhead[k] = 1 when sorted position k starts a unit
+__global__ void skp_plan_kernel(const uint64_t* __restrict__ keys, int64_t n, int32_t* __restrict__ uhead,
+                                unsigned long long* __restrict__ counts) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    if (skp_group_head(keys, k)) atomicAdd(&counts[0], 1ull);
+    uhead[k] = skp_unit_head(keys, k) ? 1 : 0;
+}
+
+// unit: {first sorted position, pairs}; counts[1] = the units
+__global__ void skp_units_kernel(const uint64_t* __restrict__ keys, int64_t n, const int32_t* __restrict__ uhead,
+                                 const int64_t* __restrict__ ubase, int2* __restrict__ units,
+                                 unsigned long long* __restrict__ counts) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int u = uhead[k];
+    const int64_t b = ubase[k];
+    if (k == n - 1) counts[1] = (unsigned long long)(b + u);   // <= n: a unit holds a pair at least
+    if (u) units[b] = make_int2((int)k, skp_unit_pairs(keys, n, k));
+}
+
+// Rows index (asig, aoff), columns (bsig, boff). A workgroup holds up to
+// `nrows` (<= kRows) consecutive units at a time; LDS: sm holds (nrows + kNW) sw
+// dwords, the units' row signatures first, then a slice a wave.
+// 8 waves a SIMD are two workgroups a CU: the registers are held to that
+template <bool LDS>
+__global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(8, 8))) void sketch_pairs_kernel(
+    const int32_t* __restrict__ asig, const int64_t* __restrict__ aoff, const int32_t* __restrict__ bsig,
+    const int64_t* __restrict__ boff, int width, int sw, int nrows, const uint64_t* __restrict__ keys,
+    const int32_t* __restrict__ vals, const int64_t* __restrict__ cols, const int2* __restrict__ units,
+    const unsigned long long* __restrict__ counts, int jaccard, int empty_nan, int32_t* __restrict__ common_out,
+    double* __restrict__ D) {
+    extern __shared__ int32_t sm[];
+    __shared__ int64_t s_k0[kRows], s_rb[kRows];
+    __shared__ int s_la[kRows], s_np[kRows];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nunits = (int64_t)counts[1];
+    // units a step: as many as fit while every workgroup still gets a few steps
+    const int64_t share = nunits / ((int64_t)kStepsPerWg * gridDim.x);
+    const int R = (int)(share < 1 ? 1 : (share > nrows ? nrows : share));
+    int32_t* mine = sm + (nrows + wave) * sw;
+    for (int64_t u0 = (int64_t)blockIdx.x * R; u0 < nunits; u0 += (int64_t)gridDim.x * R) {
+        const int nu = (int)(nunits - u0 < R ? nunits - u0 : R);
+        __syncthreads();   // the previous step's pairs are done with the rows and their table
+        if ((int)threadIdx.x < nu) {
+            const int2 un = units[u0 + threadIdx.x];
+            const int64_t i = (int64_t)keys[un.x];
+            const int64_t rb = aoff[i], rl = aoff[i + 1] - rb;
+            s_k0[threadIdx.x] = un.x;
+            s_np[threadIdx.x] = un.y;                           // 1 .. kSkpUnitPairs
+            s_rb[threadIdx.x] = rb;
+            s_la[threadIdx.x] = (int)(rl < width ? rl : width);   // no signature is longer than the width
+        }
+        __syncthreads();
+        if (LDS) {
+            for (int r = 0; r < nu; r++) {
+                const int32_t* src = asig + s_rb[r];
+                const int la = s_la[r];
+                for (int e = threadIdx.x; e < la; e += kNT) sm[r * sw + e] = src[e];
+            }
+            __syncthreads();
+        }
+        int total = 0;
+        for (int r = 0; r < nu; r++) total += s_np[r];
+        // the step's pairs, unit after unit, to the waves in turn
+        for (int t = wave; t < total; t += kNW) {
+            int r = 0, first = 0;
+            while (r + 1 < nu && t >= first + s_np[r]) first += s_np[r++];
+            const int32_t pos = vals[s_k0[r] + (t - first)];
+            const int64_t j = cols[pos];
+            const int64_t cb = boff[j], cl = boff[j + 1] - cb;
+            const int la = s_la[r], lb = (int)(cl < width ? cl : width);
+            const int32_t *Q = asig + s_rb[r], *S = bsig + cb;
+            if (LDS) {
+                const int32_t* src = bsig + cb;
+                wave_sync();   // the wave's previous pair is done with the slice
+                constexpr int U = 4;   // loads in flight a lane
+                for (int e0 = lane; e0 < lb; e0 += 64 * U) {
+                    int32_t v[U];
+#pragma unroll
+                    for (int q = 0; q < U; q++) v[q] = e0 + q * 64 < lb ? src[e0 + q * 64] : 0;
+#pragma unroll
+                    for (int q = 0; q < U; q++)
+                        if (e0 + q * 64 < lb) mine[e0 + q * 64] = v[q];
+                }
+                wave_sync();
+                Q = sm + r * sw;
+                S = mine;
+            }
+            int common;
+            double d;
+            skx_pair_merge(Q, la, S, lb, width, jaccard, empty_nan, lane, &common, &d);
+            if (lane == 0) {
+                if (common_out) common_out[pos] = common;
+                if (D) D[pos] = d;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+// every argument checked by the caller, n > 0; rows / cols / common_out / D_out:
+// host, n entries, either output may be null
+void sketch_pairs(gdist_ctx* ctx, const gdist_sets* a, const gdist_sets* b, unsigned flags, int64_t n,
+                  const int64_t* rows, const int64_t* cols, int32_t* common_out, double* D_out) {
+    hipStream_t st = ctx->stream;
+    const bool timed = ctx->option(OPT_TIME_KERNELS, 0) != 0;
+    ctx->pairs_kernel_ms = -1.0;
+    ctx->pairs_groups = ctx->pairs_units = 0;
+    // one upload: rows, then cols
+    std::vector<int64_t> hin((size_t)2 * n);
+    std::copy(rows, rows + n, hin.begin());
+    std::copy(cols, cols + n, hin.begin() + n);
+    DevBuf din((size_t)2 * n * 8, st);
+    DevBuf k0((size_t)n * 8, st), k1((size_t)n * 8, st), v0((size_t)n * 4, st), v1((size_t)n * 4, st);
+    DevBuf uhead((size_t)n * 4, st), ubase((size_t)n * 8, st), units((size_t)n * sizeof(int2), st);
+    // one download: {groups, units}, common, D
+    const size_t c_at = 16, d_at = c_at + (common_out ? ((size_t)n * 4 + 7) & ~(size_t)7 : 0);
+    const size_t out_bytes = d_at + (D_out ? (size_t)n * 8 : 0);
+    DevBuf dout(out_bytes, st);
+    auto* counts = dout.as<unsigned long long>();
+    int32_t* dC = common_out ? reinterpret_cast<int32_t*>(static_cast<char*>(dout.p) + c_at) : nullptr;
+    double* dD = D_out ? reinterpret_cast<double*>(static_cast<char*>(dout.p) + d_at) : nullptr;
+    const int64_t* drows = din.as<int64_t>();
+    const int64_t* dcols = drows + n;
+    h2d(din.p, hin.data(), (size_t)2 * n * 8, st);
+
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EvGuard {
+        hipEvent_t* e;
+        ~EvGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
+    } guard{ev};
+    if (timed) {
+        for (auto& e : ev) GD_HIP(hipEventCreate(&e));
+        GD_HIP(hipEventRecord(ev[0], st));
+    }
+    const unsigned g256 = (unsigned)ceil_div(n, 256);
+    GD_HIP(hipMemsetAsync(dout.p, 0, c_at, st));           // the counts
+    uint64_t *keys = k0.as<uint64_t>(), *kalt = k1.as<uint64_t>();
+    int32_t *vals = v0.as<int32_t>(), *valt = v1.as<int32_t>();
+    skp_keys_kernel<<<g256, 256, 0, st>>>(drows, n, keys, vals);
+    GD_HIP(hipGetLastError());
+    int eb = 1;
+    while (eb < 64 && (int64_t(1) << eb) < a->nsets) eb++;
+    sort_pairs_u64_i32(ctx, keys, kalt, vals, valt, (size_t)n, 0, eb);
+    skp_plan_kernel<<<g256, 256, 0, st>>>(keys, n, uhead.as<int32_t>(), counts);
+    GD_HIP(hipGetLastError());
+    exclusive_scan_i32_to_i64(ctx, uhead.as<int32_t>(), ubase.as<int64_t>(), (size_t)n);
+    skp_units_kernel<<<g256, 256, 0, st>>>(keys, n, uhead.as<int32_t>(), ubase.as<int64_t>(), units.as<int2>(),
+                                           counts);
+    GD_HIP(hipGetLastError());
+
+    const int width = std::max(1, a->width), sw = width | 1;
+    // rows a step: what fits beside the 16 slices, at most kRows; none: the global variant
+    const int fit = kLdsBytes / 4 / sw - kNW;
+    const int nrows = fit >= 1 ? std::min(kRows, fit) : kRows;
+    const int jaccard = (flags & GDIST_SKETCH_JACCARD) ? 1 : 0, empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
+    const unsigned grid = (unsigned)std::min<int64_t>(n, (int64_t)std::max(ctx->cus, 1) * kWgPerCu);
+    if (fit >= 1) {
+        const size_t bytes = (size_t)(nrows + kNW) * sw * 4;   // <= kLdsBytes
+        auto kern = &sketch_pairs_kernel<true>;
+        GD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   kLdsBytes));
+        kern<<<grid, kNT, bytes, st>>>(a->codes.as<int32_t>(), a->off.as<int64_t>(), b->codes.as<int32_t>(),
+                                       b->off.as<int64_t>(), width, sw, nrows, keys, vals, dcols, units.as<int2>(),
+                                       counts, jaccard, empty_nan, dC, dD);
+    } else {
+        sketch_pairs_kernel<false><<<grid, kNT, 0, st>>>(
+            a->codes.as<int32_t>(), a->off.as<int64_t>(), b->codes.as<int32_t>(), b->off.as<int64_t>(), width, sw,
+            nrows, keys, vals, dcols, units.as<int2>(), counts, jaccard, empty_nan, dC, dD);
+    }
+    GD_HIP(hipGetLastError());
+    if (timed) GD_HIP(hipEventRecord(ev[1], st));
+    std::vector<char> hout(out_bytes);
+    d2h(hout.data(), dout.p, out_bytes, st);
+    if (timed) {
+        float ms = 0;
+        GD_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        ctx->pairs_kernel_ms = ms;
+    }
+    const auto* hc = reinterpret_cast<const unsigned long long*>(hout.data());
+    ctx->pairs_groups = (int64_t)hc[0];
+    ctx->pairs_units = (int64_t)hc[1];
+    if (common_out) std::memcpy(common_out, hout.data() + c_at, (size_t)n * 4);
+    if (D_out) std::memcpy(D_out, hout.data() + d_at, (size_t)n * 8);
+}
+
+}  // namespace gdist

@@ -60,13 +60,14 @@ def tree_source_hash() -> str:
     """sha256 prefix of the library's sources in this tree, in the Makefile's
     order (csrc/*.hip by name, csrc/gdist_internal.hpp, csrc/sparse_bounds.hpp,
     csrc/group_stats_host.hpp, csrc/cross_plan.hpp, csrc/sketch_cross_merge.hpp,
-    include/gdist.h)."""
+    csrc/sketch_wave_merge.hpp, csrc/sketch_pairs_plan.hpp, include/gdist.h)."""
     import glob
     import hashlib
     files = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hip")))
     files += [os.path.join(_PKG, "csrc", "gdist_internal.hpp"), os.path.join(_PKG, "csrc", "sparse_bounds.hpp"),
               os.path.join(_PKG, "csrc", "group_stats_host.hpp"), os.path.join(_PKG, "csrc", "cross_plan.hpp"),
-              os.path.join(_PKG, "csrc", "sketch_cross_merge.hpp"), os.path.join(_REPO, "include", "gdist.h")]
+              os.path.join(_PKG, "csrc", "sketch_cross_merge.hpp"), os.path.join(_PKG, "csrc", "sketch_wave_merge.hpp"),
+              os.path.join(_PKG, "csrc", "sketch_pairs_plan.hpp"), os.path.join(_REPO, "include", "gdist.h")]
     h = hashlib.sha256()
     for f in files:
         with open(f, "rb") as fh:
@@ -144,6 +145,7 @@ _SIGS = {
     "gdist_sketch_upload": (C.c_int, [_ctxp, C.c_int, _i64, _i64p, _i32p, C.POINTER(_setp)]),
     "gdist_sketch_download": (C.c_int, [_setp, _i64p, _i32p]),
     "gdist_sketch_matrix": (C.c_int, [_ctxp, _setp, _i64, _i64, _i64, _i64, _u32, _vp, _vp, _i64]),
+    "gdist_sketch_pairs": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64p, _i64p, _u32, _i32p, _dblp]),
     "gdist_lsh_build": (C.c_int, [_ctxp, _setp, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]),
     "gdist_lsh_free": (C.c_int, [C.c_void_p]),
     "gdist_lsh_closest": (C.c_int, [_ctxp, C.c_void_p, _setp, C.c_int, _dbl, _i64p, _dblp, _i32p]),

@@ -1188,6 +1188,27 @@ class SequenceKmers:
         return self.sets.sketches(width).signature(self.index)
 
 
+def reduce_row_query(D, mode: int = L.QUERY_ALL, t: float = 1.0):
+    """The reductions gdist_row_query documents, on a row of distances already
+    on the host (SketchSets.row_query). ALL: the distances as they are. ANY_LE:
+    True when any distance is <= t. ARGMIN: (position, distance) of the
+    smallest distance, ties to the lowest position; (-1, 1.0) when no distance
+    is below 1.0 (the reference's NULL_RESULT identity wins ties at 1.0).
+    NaN never qualifies, in either mode."""
+    D = np.asarray(D, dtype=np.float64).reshape(-1)
+    if mode == L.QUERY_ALL:
+        return D
+    if mode == L.QUERY_ANY_LE:
+        return bool(np.any(D <= t))            # a comparison with NaN is False
+    if mode != L.QUERY_ARGMIN:
+        raise ValueError(f"unknown row query mode {mode}")
+    ok = D < 1.0
+    if not ok.any():
+        return -1, 1.0
+    i = int(np.argmin(np.where(ok, D, np.inf)))   # the first of equal minima
+    return i, float(D[i])
+
+
 class SketchSets(_Handle):
     """Bottom-s MinHash signatures (int32) resident in HBM."""
 
@@ -1304,6 +1325,49 @@ class SketchSets(_Handle):
         distributed (gdist_cross_histogram): as KmerSets.cross_histogram."""
         return self._cross_histogram(queries, edges, qlabels, slabels, rows, cols,
                                      flags | (L.EMPTY_NAN if empty_nan else 0))
+
+    def pairs(self, rows, cols, other: "SketchSets | None" = None, flags: int = 0, want_common: bool = True,
+              want_D: bool = True):
+        """Sketch distances of a pair list (gdist_sketch_pairs): for every p the
+        common count and sketch distance of signature rows[p] of this
+        collection and signature cols[p] of `other` (default: this collection),
+        in one device call: (common int32[P] | None, D float64[P] | None). Any
+        order, repeats and (with one collection) i == j allowed; both are
+        other.cross_matrix(self)'s cell (rows[p], cols[p]) bit for bit, with one
+        collection matrix()'s. flags: SKETCH_JACCARD, EMPTY_NAN."""
+        b = self if other is None else other
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        c = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
+        if len(r) != len(c):
+            raise ValueError(f"{len(r)} rows but {len(c)} cols")
+        n = len(r)
+        common = np.full(n, -1, dtype=np.int32) if want_common else None
+        D = np.full(n, np.nan, dtype=np.float64) if want_D else None
+        L.check(L.lib.gdist_sketch_pairs(self.ctx.h, self.h, b.h, n, L.ptr(r, C.c_int64) if n else None,
+                                         L.ptr(c, C.c_int64) if n else None, flags,
+                                         L.ptr(common, C.c_int32) if want_common and n else None,
+                                         L.ptr(D, C.c_double) if want_D and n else None))
+        return common, D
+
+    def pairs_info(self) -> tuple[float, int, int]:
+        """(kernel ms, groups, units) of the context's last pair-list call
+        (gdist_ctx_pairs_info): the kernel time is -1 unless option
+        time_kernels = 1; groups are the distinct rows of the list, units the
+        sum over them of ceil(pairs of the row / 64)."""
+        ms, g, u = C.c_double(), C.c_int64(), C.c_int64()
+        L.check(L.lib.gdist_ctx_pairs_info(self.ctx.h, C.byref(ms), C.byref(g), C.byref(u)))
+        return ms.value, g.value, u.value
+
+    def row_query(self, q: int, cols: Iterable[int], mode: int = L.QUERY_ALL, t: float = 1.0,
+                  other: "SketchSets | None" = None):
+        """Signature q of this collection against signatures cols[] of `other`
+        (default: this collection): one pair list with rows = [q] * len(cols),
+        reduced on the host by the rules of gdist_row_query (reduce_row_query).
+        ALL: the distances; ANY_LE: whether any is <= t; ARGMIN: (position in
+        cols, distance), (-1, 1.0) when none is below 1.0."""
+        cl = np.ascontiguousarray(np.fromiter(cols, dtype=np.int64))
+        _, D = self.pairs(np.full(len(cl), q, dtype=np.int64), cl, other=other, want_common=False)
+        return reduce_row_query(D, mode, t)
 
     def matrix_device(self, d_common: int | None, d_D: int | None, ld: int, rows, cols, upper=False, flags=0):
         fl = flags | L.OUT_DEVICE | (L.UPPER_TRIANGLE if upper else 0)

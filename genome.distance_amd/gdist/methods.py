@@ -27,6 +27,10 @@ unpinned): the kmer methods' type names and parameter syntax
 appearance of id1, pairs of a group in input order), TaxonDistanceMethod's
 grouping level (deepest shared lineage rank) and CorrelationVariance's
 variation / IQR (mean |d1 - d2| and the interquartile range of d1 - d2).
+The `minhash` type (MinHashMethod, "K=21,W=1000", header "MINHASH_K21_W1000")
+is not a reference type at all: it is the sketch column next to the exact
+kmer column, the comparison the reference makes in its width command, answered
+for a whole pair list by one gdist_sketch_pairs call.
 """
 from __future__ import annotations
 
@@ -197,6 +201,86 @@ class ProteinKmerMethod(_KmerMethod):
 
     def kmer_text(self, g: Genome) -> bytes:
         return b"\0".join(p.encode("latin-1") for p in (g.proteins or []))
+
+
+class MinHashMethod(_KmerMethod):
+    """MinHash sketch distance of the contig DNA kmers: the sketch column next
+    to the exact kmer column. Not a reference method type (the reference's
+    methods table has no sketch column; its sketches meet the exact distance in
+    the width comparison): every genome of a list is packed once, the sketches
+    are built once and ONE gdist_sketch_pairs call answers the list."""
+    type_name = "minhash"
+    default_width = 1000
+
+    def __init__(self, ctx=None):
+        super().__init__(ctx)
+        self.width = self.default_width
+        self.pair_calls = 0                   # gdist_sketch_pairs calls made
+        self.last_info = None                 # pairs_info() read after the last one
+
+    def parseParmString(self, parms: str) -> None:
+        for tok in (parms or "").replace(",", " ").split():
+            key, _, val = tok.partition("=")
+            if key.upper() in ("K", "KMER", "KMERSIZE"):
+                try:
+                    self.k = int(val)
+                except ValueError:
+                    raise ParseFailureException(f"Invalid kmer size \"{val}\" for {self.type_name}.") from None
+            elif key.upper() in ("W", "WIDTH"):
+                try:
+                    self.width = int(val)
+                except ValueError:
+                    raise ParseFailureException(f"Invalid sketch width \"{val}\" for {self.type_name}.") from None
+            else:
+                raise ParseFailureException(f"Invalid parameter \"{tok}\" for {self.type_name}.")
+        if self.k < 2:
+            raise ParseFailureException("Kmer size must be at least 2.")
+        if self.width < 1:
+            raise ParseFailureException("Sketch width must be at least 1.")
+
+    def __str__(self) -> str:
+        return f"MINHASH_K{self.k}_W{self.width}"
+
+    def kmer_text(self, g: Genome) -> bytes:
+        return g.kmer_text()
+
+    def _list_distances(self, texts: Sequence[bytes], rows, cols) -> list[float]:
+        """One pack, one sketch build, one device pair-list call."""
+        sets = KmerSets.from_sequences(list(texts), self.k, self.kmer_type, self.flags, self.ctx)
+        sk = None
+        try:
+            sk = sets.sketches(self.width)
+            _, d = sk.pairs(rows, cols, want_common=False)
+            self.pair_calls += 1
+            self.last_info = sk.pairs_info()
+        finally:
+            if sk is not None:
+                sk.free()
+            sets.free()
+        return [float(x) for x in d]
+
+    def getDistances(self, measurer: Measurer, genomes: Sequence[Genome]) -> list[float]:
+        """The measurer's genome (set 0) against `genomes`: one pair list of
+        one row."""
+        if not genomes:
+            return []
+        n = len(genomes)
+        return self._list_distances([measurer.text] + [self.kmer_text(g) for g in genomes], [0] * n,
+                                    list(range(1, 1 + n)))
+
+    def pair_distances(self, pairs: Sequence[tuple[Genome, Genome]]) -> list[float]:
+        """The sketch distances of a whole pair list: every genome of the list
+        packed once (first appearance), their sketches built once, then ONE
+        gdist_sketch_pairs call over the (id1, id2) positions."""
+        if not pairs:
+            return []
+        index: dict[str, int] = {}
+        texts = []
+        for g in (g for p in pairs for g in p):
+            if g.id not in index:
+                index[g.id] = len(texts)
+                texts.append(self.kmer_text(g))
+        return self._list_distances(texts, [index[a.id] for a, _ in pairs], [index[b.id] for _, b in pairs])
 
 
 class TaxonDistanceMethod:

@@ -24,6 +24,10 @@
  *                          sequential early exit                 FastaDistanceRepsProcessor.java:117-128
  *   gdist_sketch_build     SequenceKmers.hashSet(width)          SketchProcessor.java:88, WidthProcessor.java:178
  *   gdist_sketch_matrix    Sketch.distance(other) all-pairs      WidthProcessor.java:183-185, TuningProcessor.java:131-133
+ *   gdist_sketch_pairs     Sketch.distance(other) over an (id1, id2)
+ *                          list, beside the exact kmer column    MethodTableProcessor.java:258-276
+ *                          the sketch-against-exact comparison
+ *                          over chosen pairs                     WidthProcessor.java:183-192
  *   gdist_closest          getClosest(kmers, n, maxDist), exhaustively
  *                          (every column, no LSH buckets)        MashProcessor.java:150, FindProcessor.java:110
  *                          --maxDist of the genomes table        GenomeProcessor.java:58-60,89
@@ -378,6 +382,41 @@ int  gdist_sketch_download(const gdist_sets* sk, int64_t* offsets, int32_t* sigs
 int  gdist_sketch_matrix(gdist_ctx* ctx, const gdist_sets* sk,
                          int64_t r0, int64_t r1, int64_t c0, int64_t c1, unsigned flags,
                          int32_t* common_out, double* D_out, int64_t ld);
+/* Sketch.distance over a pair list (MethodTableProcessor.java:258-276; the
+ * chosen pairs of WidthProcessor.java:183-192): for p in [0, npairs)
+ * common_out[p] and D_out[p] are the common count and the sketch distance of
+ * signature rows[p] of `a` and signature cols[p] of `b`, host arrays, either
+ * may be NULL. `a` and `b` are two GDIST_SKETCH collections of `ctx` with one
+ * width and one kmer spec (what gdist_sets_concat accepts); the same handle
+ * may be passed for both (the one-collection pair list). Both are only read:
+ * nothing is built or kept on either.
+ *
+ * The list may come in any order, may repeat a pair and, with one handle, may
+ * hold i == j: output slot p depends on (rows[p], cols[p], flags) only, not on
+ * the order, the rest of the list or the run. Both outputs are bit for bit
+ * what gdist_cross_matrix(ctx, a, b, ...) writes for cell (rows[p], cols[p])
+ * with the same flags; with one handle that is gdist_sketch_matrix's cell, for
+ * i == j the diagonal one (common = the signature's length, d = 0.0, or the
+ * empty value of an empty signature). flags: GDIST_EMPTY_NAN and
+ * GDIST_SKETCH_JACCARD, as in gdist_sketch_matrix.
+ *
+ * The list is uploaded once, sorted by row on the device and cut into work
+ * units there (a row and at most 64 of its pairs; a signature is at most
+ * `width` hashes, so a pair is never split); a workgroup stages a unit's row
+ * signature on chip once and a wave merges each of its pairs; the outputs come
+ * back in one download and nothing at or past npairs is touched.
+ * gdist_ctx_pairs_info then reports this call: groups = the distinct rows of
+ * the list, units = the sum over them of ceil(pairs of the row / 64).
+ * npairs == 0: GDIST_OK, nothing is touched (rows and cols may be NULL).
+ * EINVAL, decided before any work (the outputs stay untouched): a null handle,
+ * a handle of another context, a collection of kmer sets on either side
+ * (gdist_pairs takes those), widths or kmer specs gdist_sets_concat would
+ * refuse, npairs < 0 or >= 2^31, null rows or cols or both outputs null with
+ * npairs > 0, any other flag, a rows[p] outside [0, nsets of a), a cols[p]
+ * outside [0, nsets of b). */
+int  gdist_sketch_pairs(gdist_ctx* ctx, const gdist_sets* a, const gdist_sets* b, int64_t npairs,
+                        const int64_t* rows /* into a */, const int64_t* cols /* into b */, unsigned flags,
+                        int32_t* common_out, double* D_out);
 
 /* ---- LSH bucket query (MashProcessor / FindProcessor) ------------------ */
 /* Index of a sketch collection: new LSHMemSeqHash(width, stages, buckets)
@@ -552,7 +591,7 @@ int  gdist_ctx_within_timing(gdist_ctx* ctx, double* matrix_ms, double* select_m
 int  gdist_pairs(gdist_ctx* ctx, const gdist_sets* sets, int64_t npairs,
                  const int64_t* rows, const int64_t* cols, int method, unsigned flags,
                  int32_t* I_out, double* D_out);
-/* last gdist_pairs call: kernel time (ms; -1 unless option "time_kernels" = 1), the
+/* last gdist_pairs or gdist_sketch_pairs call: kernel time (ms; -1 unless option "time_kernels" = 1), the
  * distinct-row groups of the list and the work units launched for them */
 int  gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, int64_t* units);
 
