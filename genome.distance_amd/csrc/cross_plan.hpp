@@ -7,7 +7,7 @@
 // column block, segment range [p0, p1) of the subjects' segment index). A
 // (row, block) whose codes |Q_i| + sum |S_j| exceed the budget is cut into
 // u = clamp(ceil(codes / budget), 1, nseg) even ranges nseg t / u, as
-// pairs_units_kernel (pairs.hip) cuts a chunk of a pair list; the units of one
+// pl_unit_seg (pair_list.hpp) cuts a chunk of a pair list; the units of one
 // (row, block) add their integer counts into the same cells, which is exact.
 // A row whose set is empty gets no unit: its cells stay zero.
 //

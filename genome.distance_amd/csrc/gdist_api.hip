@@ -1199,7 +1199,6 @@ int gdist_greedy_reps(gdist_ctx* ctx, const gdist_sets* sets, int method, double
         GD_REQUIRE(sets->kind != GDIST_SKETCH, "representatives are chosen on kmer sets");
         GD_REQUIRE(is_rep != nullptr, "is_rep is required");
         GD_REQUIRE(method >= GDIST_METHOD_AUTO && method <= GDIST_METHOD_BITSET, "unknown method");
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
         auto* s = const_cast<gdist_sets*>(sets);
         const int64_t n = s->nsets;
         const int m = resolve_method(ctx, s, method, (double)n * (double)n);
@@ -1220,7 +1219,6 @@ int gdist_row_query(gdist_ctx* ctx, const gdist_sets* sets, int64_t q, const int
         GD_REQUIRE(ncols >= 0 && (ncols == 0 || cols), "bad column list");
         GD_REQUIRE(mode >= GDIST_QUERY_ALL && mode <= GDIST_QUERY_ARGMIN, "unknown query mode");
         for (int64_t c = 0; c < ncols; c++) GD_REQUIRE(cols[c] >= 0 && cols[c] < sets->nsets, "column index out of range");
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
         auto* s = const_cast<gdist_sets*>(sets);
         GD_REQUIRE(s->bits.p || s->has_codes, "this collection holds bitsets only");
         hipStream_t st = ctx->stream;
@@ -1363,37 +1361,6 @@ int gdist_sketch_matrix(gdist_ctx* ctx, const gdist_sets* sk, int64_t r0, int64_
     });
 }
 
-int gdist_sketch_pairs(gdist_ctx* ctx, const gdist_sets* a, const gdist_sets* b, int64_t npairs, const int64_t* rows,
-                       const int64_t* cols, unsigned flags, int32_t* common_out, double* D_out) {
-    return guard([&] {
-        use_device(ctx);
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        check_sets(a);
-        check_sets(b);
-        GD_REQUIRE(a->ctx == ctx && b->ctx == ctx, "sketches belong to another context");
-        GD_REQUIRE(a->kind == GDIST_SKETCH && b->kind == GDIST_SKETCH,
-                   "sketch pair lists run on two GDIST_SKETCH collections (kmer sets: gdist_pairs)");
-        check_same_spec(a, b);
-        check_codes(a);
-        check_codes(b);
-        GD_REQUIRE(npairs >= 0 && npairs < (int64_t(1) << 31), "npairs outside 0 .. 2^31 - 1");
-        GD_REQUIRE(!(flags & ~(GDIST_EMPTY_NAN | GDIST_SKETCH_JACCARD)),
-                   "gdist_sketch_pairs takes no flag but GDIST_EMPTY_NAN and GDIST_SKETCH_JACCARD");
-        GD_REQUIRE(npairs == 0 || (rows && cols), "null rows or cols");
-        GD_REQUIRE(npairs == 0 || common_out || D_out, "both outputs null");
-        for (int64_t p = 0; p < npairs; p++) {
-            GD_REQUIRE(rows[p] >= 0 && rows[p] < a->nsets, "row index outside the first collection");
-            GD_REQUIRE(cols[p] >= 0 && cols[p] < b->nsets, "column index outside the second collection");
-        }
-        ctx->pairs_kernel_ms = -1.0;
-        ctx->pairs_groups = ctx->pairs_units = 0;
-        if (npairs == 0) return;
-        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
-        ctx->last = Timing{};
-        gdist::sketch_pairs(ctx, a, b, flags, npairs, rows, cols, common_out, D_out);
-    });
-}
-
 // ---------------------------------------------------------------------------
 int gdist_lsh_build(gdist_ctx* ctx, const gdist_sets* sketches, int stages, int buckets, uint64_t seed,
                     gdist_lsh** out) {
@@ -1482,6 +1449,21 @@ static void closest_none(int64_t nr, int n, int64_t* idx_out, double* d_out, int
 static void begin_call(gdist_ctx* ctx) {
     ctx->pending = false;          // an unread previous call's times are dropped, not waited for
     ctx->last = Timing{};
+}
+
+// what gdist_pairs and gdist_sketch_pairs refuse of their list alike; past it
+// gdist_ctx_pairs_info is this call's
+static void begin_pairs(gdist_ctx* ctx, int64_t npairs, const int64_t* rows, int64_t nrows, const char* row_msg,
+                        const int64_t* cols, int64_t ncols, const char* col_msg, const void* out_a, const void* out_b) {
+    GD_REQUIRE(npairs >= 0 && npairs < (int64_t(1) << 31), "npairs outside 0 .. 2^31 - 1");
+    GD_REQUIRE(npairs == 0 || (rows && cols), "null rows or cols");
+    GD_REQUIRE(npairs == 0 || out_a || out_b, "both outputs null");
+    for (int64_t p = 0; p < npairs; p++) {
+        GD_REQUIRE(rows[p] >= 0 && rows[p] < nrows, row_msg);
+        GD_REQUIRE(cols[p] >= 0 && cols[p] < ncols, col_msg);
+    }
+    ctx->pairs_kernel_ms = -1.0;
+    ctx->pairs_groups = ctx->pairs_units = 0;
 }
 
 // what every gdist_cross_* call refuses alike, before any work
@@ -1640,24 +1622,40 @@ int gdist_pairs(gdist_ctx* ctx, const gdist_sets* sets, int64_t npairs, const in
         check_sets(sets);
         GD_REQUIRE(sets->ctx == ctx, "sets belong to another context");
         GD_REQUIRE(sets->kind != GDIST_SKETCH, "pair lists run on kmer sets");
-        GD_REQUIRE(npairs >= 0 && npairs < (int64_t(1) << 31), "npairs outside 0 .. 2^31 - 1");
         GD_REQUIRE(!(flags & (GDIST_UPPER_TRIANGLE | GDIST_OUT_DEVICE)),
                    "gdist_pairs supports neither GDIST_UPPER_TRIANGLE nor GDIST_OUT_DEVICE");
         GD_REQUIRE(method >= GDIST_METHOD_AUTO && method <= GDIST_METHOD_BITSET, "unknown method");
         GD_REQUIRE(method != GDIST_METHOD_SORTED || sets->has_codes, "this collection holds bitsets only");
-        GD_REQUIRE(npairs == 0 || (rows && cols), "null rows or cols");
-        GD_REQUIRE(npairs == 0 || I_out || D_out, "both outputs null");
-        for (int64_t p = 0; p < npairs; p++)
-            GD_REQUIRE(rows[p] >= 0 && rows[p] < sets->nsets && cols[p] >= 0 && cols[p] < sets->nsets,
-                       "pair index out of range");
-        ctx->pairs_kernel_ms = -1.0;
-        ctx->pairs_groups = ctx->pairs_units = 0;
+        begin_pairs(ctx, npairs, rows, sets->nsets, "pair index out of range", cols, sets->nsets,
+                    "pair index out of range", I_out, D_out);
         if (npairs == 0) return;
         auto* s = const_cast<gdist_sets*>(sets);
         const int m = resolve_method(ctx, s, method, (double)npairs);
-        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
-        ctx->last = Timing{};
+        begin_call(ctx);
         gdist::pairs(ctx, s, m, flags, npairs, rows, cols, I_out, D_out);
+    });
+}
+
+int gdist_sketch_pairs(gdist_ctx* ctx, const gdist_sets* a, const gdist_sets* b, int64_t npairs, const int64_t* rows,
+                       const int64_t* cols, unsigned flags, int32_t* common_out, double* D_out) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_sets(a);
+        check_sets(b);
+        GD_REQUIRE(a->ctx == ctx && b->ctx == ctx, "sketches belong to another context");
+        GD_REQUIRE(a->kind == GDIST_SKETCH && b->kind == GDIST_SKETCH,
+                   "sketch pair lists run on two GDIST_SKETCH collections (kmer sets: gdist_pairs)");
+        check_same_spec(a, b);
+        check_codes(a);
+        check_codes(b);
+        GD_REQUIRE(!(flags & ~(GDIST_EMPTY_NAN | GDIST_SKETCH_JACCARD)),
+                   "gdist_sketch_pairs takes no flag but GDIST_EMPTY_NAN and GDIST_SKETCH_JACCARD");
+        begin_pairs(ctx, npairs, rows, a->nsets, "row index outside the first collection", cols, b->nsets,
+                    "column index outside the second collection", common_out, D_out);
+        if (npairs == 0) return;
+        begin_call(ctx);
+        gdist::sketch_pairs(ctx, a, b, flags, npairs, rows, cols, common_out, D_out);
     });
 }
 

@@ -927,6 +927,42 @@ void hist_count(gdist_ctx* ctx, WalkSource& src, int64_t r0, int64_t r1, int64_t
                 const double* edges, int ntypes, const int32_t* rlabels, const int32_t* clabels, int64_t* counts,
                 int64_t* nans, int64_t* bad);
 
+// pair_list.hip — what gdist_pairs and gdist_sketch_pairs do alike: the list
+// on the device, sorted by row and cut into units (pair_list.hpp), the packed
+// outputs, gdist_ctx_pairs_info. A call constructs the list (one upload), plans
+// it one way, queues its consumer kernels on ctx->stream and finishes (one
+// download). No host round trip in between: consumers read counts[1].
+struct PairList {
+    gdist_ctx* ctx;
+    int64_t n, nsets;                  // pairs (> 0); sets the rows index
+    const int64_t *rows, *cols;        // device: the list as given
+    uint64_t* keys = nullptr;          // planned: the rows ascending (stable), and
+    int32_t* vals = nullptr;           //   each sorted position's place in the list
+    unsigned long long* counts;        // device: {groups, units}
+    int32_t* I;                        // device [n], null when not kept
+    double* D;                         // device [n], null when not wanted
+    DevBuf units;                      // planned: counts[1] unit records, ucap at most
+    int64_t ucap = 0;
+    // I_out / D_out: host, n entries, either may be null. need_I: the consumers
+    // add into a zeroed I whether or not it is wanted
+    PairList(gdist_ctx* ctx, int64_t nsets, int64_t n, const int64_t* rows, const int64_t* cols, int32_t* I_out,
+             double* D_out, bool need_I);
+    ~PairList();
+    void plan_groups();                // no units: a pair is a unit of work
+    void plan_units();                 // int2 {first sorted position, pairs}: a chunk
+    // int4 {first sorted position, pairs, first segment, end segment}: a chunk of the
+    // collection s cut by its codes; codes: the list's, over its pairs, both sets
+    void plan_segment_units(const gdist_sets* s, double codes);
+    void finish();
+
+    DevBuf in, k0, k1, v0, v1, ucount, ubase, out;
+    size_t i_at, d_at;
+    int32_t* I_out;
+    double* D_out;
+    bool zero_I, timed;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
 // pairs.hip — the distances of a pair list (gdist_pairs)
 // method: SORTED or BITSET (resolved by the caller, every argument checked);
 // rows / cols / I_out / D_out: host, n entries, either output may be null

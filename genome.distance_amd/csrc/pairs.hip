@@ -5,18 +5,15 @@
 // intersections, one upload, one download. The rectangle kernels do not fit:
 // a list of many first genomes with a handful of partners each fills no tile.
 //
-// Plan (on the device, no host round trip): the pair positions are sorted by
-// row (sort_pairs_u64_i32, stable: positions ascend within a row); the runs of
-// equal row are the groups. A run is cut into chunks of at most UNIT_COLS
-// consecutive pairs, and a chunk whose codes (|A_i| plus its columns' sets)
-// exceed the call's budget into several ranges of the segment index
-// (sorted.hip build_segments): the units. The budget is the list's codes over
-// UNITS_PER_CU units a CU, within [UNIT_CODES_MIN, UNIT_CODES_MAX]: a short
-// list is cut finer. A unit adds its counts into a zeroed I with
-// atomicAdd (integers: exact, order-free), so a few pairs of huge sets still
-// fill the chip. plan_kernel counts the units of each chunk start, a scan
-// places them, units_kernel writes them; the join kernel reads their number
-// from device memory and strides over them.
+// Plan (PairList, pair_list.hip: one upload, no host round trip): the pair
+// positions sorted by row and cut into chunks of at most kPairUnit pairs of
+// one row. Sorted path: a chunk whose codes (|A_i| plus its columns' sets)
+// exceed the call's budget (pair_list.hpp) is cut into several ranges of the
+// segment index (sorted.hip build_segments), the units. A unit adds its counts
+// into a zeroed I with atomicAdd (integers: exact, order-free), so a few pairs
+// of huge sets still fill the chip. The join kernel reads the number of units
+// from device memory and strides over them. Bitset path: no units, the sorted
+// positions.
 //
 // Sorted path (pairs_sorted_kernel): as sorted_join_kernel, a workgroup stages
 // A_i's codes of the unit's next segments in LDS and its waves stream the same
@@ -36,100 +33,22 @@
 // the set with fewer entries is searched for the other set in its word list
 // (ascending), a hit adds popc(mask & mask). The three sums are what
 // bitset_matrix counts; a self pair is |A_i| (the epilogue).
-#include <algorithm>
-#include <cstring>
-
 #include "gdist_internal.hpp"
+#include "pair_list.hpp"
+#include "sketch_wave_merge.hpp"
 
 namespace gdist {
 namespace {
 
-constexpr int UNIT_COLS = 64;               // pairs of one row a unit holds at most
-// codes (row + columns) past which a unit is cut by segment range: the list's
-// codes over UNITS_PER_CU units a CU, within [UNIT_CODES_MIN, UNIT_CODES_MAX]
-constexpr int64_t UNIT_CODES_MIN = 1 << 14, UNIT_CODES_MAX = 1 << 18;
-constexpr int UNITS_PER_CU = 8;
 constexpr int NTP = 512;                    // threads of a join workgroup (8 waves)
 constexpr int STAGE = 4096;                 // keys of A staged at a time (32 KiB)
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__global__ void pairs_keys_kernel(const int64_t* __restrict__ rows, int64_t n, uint64_t* __restrict__ keys,
-                                  int32_t* __restrict__ vals) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    keys[p] = (uint64_t)rows[p];
-    vals[p] = (int32_t)p;
-}
-
-// pairs of the run of keys[k] in [k, k + UNIT_COLS)
-__device__ __forceinline__ int chunk_pairs(const uint64_t* __restrict__ keys, int64_t n, int64_t k) {
-    const uint64_t key = keys[k];
-    int c = 1;
-    while (c < UNIT_COLS && k + c < n && keys[k + c] == key) c++;
-    return c;
-}
-
-// counts[0] += the run heads (groups). With budget > 0: ucount[k] = the units
-// of the chunk that starts at sorted position k (0: k starts no chunk).
-__global__ void pairs_plan_kernel(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals, int64_t n,
-                                  const int64_t* __restrict__ cols, const int64_t* __restrict__ off, int nseg,
-                                  int64_t budget, int32_t* __restrict__ ucount,
-                                  unsigned long long* __restrict__ counts) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const uint64_t key = keys[k];
-    if (k == 0 || keys[k - 1] != key) atomicAdd(&counts[0], 1ull);
-    if (budget <= 0) return;
-    int64_t lo = 0, hi = k;                 // the run's first position
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    int32_t u = 0;
-    if (((k - lo) % UNIT_COLS) == 0) {
-        const int c = chunk_pairs(keys, n, k);
-        int64_t codes = off[key + 1] - off[key];
-        for (int t = 0; t < c; t++) {
-            const int64_t j = cols[vals[k + t]];
-            codes += off[j + 1] - off[j];
-        }
-        const int64_t want = (codes + budget - 1) / budget;
-        u = (int32_t)(want < 1 ? 1 : (want > nseg ? nseg : want));
-    }
-    ucount[k] = u;
-}
-
-// unit: {first sorted position, pairs, first segment, end segment}
-__global__ void pairs_units_kernel(const uint64_t* __restrict__ keys, int64_t n, const int32_t* __restrict__ ucount,
-                                   const int64_t* __restrict__ ubase, int nseg, int64_t cap, int4* __restrict__ units,
-                                   unsigned long long* __restrict__ counts) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const int u = ucount[k];
-    const int64_t b = ubase[k];
-    if (k == n - 1) {
-        const int64_t tot = b + u;
-        counts[1] = (unsigned long long)(tot < cap ? tot : cap);
-    }
-    if (!u) return;
-    const int c = chunk_pairs(keys, n, k);
-    for (int t = 0; t < u; t++) {
-        if (b + t >= cap) return;           // defensive: the host's bound holds every unit
-        units[b + t] = make_int4((int)k, c, (int)((int64_t)nseg * t / u), (int)((int64_t)nseg * (t + 1) / u));
-    }
-}
 
 __global__ __launch_bounds__(NTP) void pairs_sorted_kernel(
     const uint64_t* __restrict__ codes, const int64_t* __restrict__ segoff, int nseg,
     const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals, const int64_t* __restrict__ cols,
     const int4* __restrict__ units, const unsigned long long* __restrict__ counts, int32_t* __restrict__ I) {
     __shared__ unsigned long long sa[STAGE];
-    __shared__ int32_t cnt[UNIT_COLS];
+    __shared__ int32_t cnt[kPairUnit];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t nunits = (int64_t)counts[1];
     const int64_t per = nseg + 1;
@@ -139,7 +58,7 @@ __global__ __launch_bounds__(NTP) void pairs_sorted_kernel(
         const int ncol = un.y;
         const int64_t i = (int64_t)keys[k0];
         const int64_t* arow = segoff + i * per;
-        if (tid < UNIT_COLS) cnt[tid] = 0;
+        if (tid < kPairUnit) cnt[tid] = 0;
         __syncthreads();
         // a unit of few columns: each column's run in S slices, a wave a slice
         const int S = ncol >= NTP / 64 ? 1 : (NTP / 64) / ncol;
@@ -173,7 +92,7 @@ __global__ __launch_bounds__(NTP) void pairs_sorted_kernel(
                         }
                         c += sa[base] == v;
                     }
-                    c = wave_sum(c);
+                    c = skx_wave_sum(c);
                     if (lane == 0 && c) atomicAdd(&cnt[t], c);
                 }
                 __syncthreads();
@@ -238,7 +157,7 @@ __global__ __launch_bounds__(256) void pairs_bitset_kernel(
                     acc += __popcll(m & vmask[f]);
             }
         }
-        acc = wave_sum(acc);
+        acc = skx_wave_sum(acc);
         if (lane == 0) I[p] = acc;
     }
 }
@@ -272,100 +191,31 @@ __global__ void pairs_epilogue_kernel(const int64_t* __restrict__ off, const int
 void pairs(gdist_ctx* ctx, const gdist_sets* s, int method, unsigned flags, int64_t n, const int64_t* rows,
            const int64_t* cols, int32_t* I_out, double* D_out) {
     hipStream_t st = ctx->stream;
-    const bool sorted = method == GDIST_METHOD_SORTED;
-    const bool timed = ctx->option(OPT_TIME_KERNELS, 0) != 0;
-    ctx->pairs_kernel_ms = -1.0;
-    ctx->pairs_groups = ctx->pairs_units = 0;
-    // one upload: rows, then cols
-    std::vector<int64_t> hin((size_t)2 * n);
-    std::copy(rows, rows + n, hin.begin());
-    std::copy(cols, cols + n, hin.begin() + n);
-    // the budget, and the most units the plan can make with it: a chunk per pair, and a cut per budget of the chunks' codes
-    int64_t ucap = 0, budget = 0;
-    if (sorted) {
+    PairList pl(ctx, s->nsets, n, rows, cols, I_out, D_out, true);   // the join adds into I, the epilogue reads it
+    if (method == GDIST_METHOD_SORTED) {
         double codes = 0;
         for (int64_t p = 0; p < n; p++)
             codes += (double)(s->h_off[rows[p] + 1] - s->h_off[rows[p]] + s->h_off[cols[p] + 1] - s->h_off[cols[p]]);
-        budget = std::max(UNIT_CODES_MIN,
-                          std::min(UNIT_CODES_MAX, (int64_t)(codes / ((double)ctx->cus * UNITS_PER_CU))));
-        ucap = n + (int64_t)(codes / (double)budget) + 1;
-    }
-    DevBuf din((size_t)2 * n * 8, st);
-    DevBuf k0((size_t)n * 8, st), k1((size_t)n * 8, st), v0((size_t)n * 4, st), v1((size_t)n * 4, st);
-    DevBuf ucount, ubase, units;
-    if (sorted) {
-        ucount.alloc((size_t)n * 4, st);
-        ubase.alloc((size_t)n * 8, st);
-        units.alloc((size_t)ucap * sizeof(int4), st);
-    }
-    // one download: {groups, units}, I, D
-    const size_t i_at = 16, d_at = i_at + (((size_t)n * 4 + 7) & ~(size_t)7);
-    const size_t out_bytes = d_at + (D_out ? (size_t)n * 8 : 0);
-    DevBuf dout(out_bytes, st);
-    auto* counts = dout.as<unsigned long long>();
-    auto* dI = reinterpret_cast<int32_t*>(static_cast<char*>(dout.p) + i_at);
-    double* dD = D_out ? reinterpret_cast<double*>(static_cast<char*>(dout.p) + d_at) : nullptr;
-    const int64_t* drows = din.as<int64_t>();
-    const int64_t* dcols = drows + n;
-    h2d(din.p, hin.data(), (size_t)2 * n * 8, st);
-
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-    } guard{ev};
-    if (timed) {
-        for (auto& e : ev) GD_HIP(hipEventCreate(&e));
-        GD_HIP(hipEventRecord(ev[0], st));
-    }
-    const unsigned g256 = (unsigned)ceil_div(n, 256);
-    GD_HIP(hipMemsetAsync(dout.p, 0, d_at, st));           // the counts and I
-    uint64_t *keys = k0.as<uint64_t>(), *kalt = k1.as<uint64_t>();
-    int32_t *vals = v0.as<int32_t>(), *valt = v1.as<int32_t>();
-    pairs_keys_kernel<<<g256, 256, 0, st>>>(drows, n, keys, vals);
-    GD_HIP(hipGetLastError());
-    int eb = 1;
-    while (eb < 64 && (int64_t(1) << eb) < s->nsets) eb++;
-    sort_pairs_u64_i32(ctx, keys, kalt, vals, valt, (size_t)n, 0, eb);
-    pairs_plan_kernel<<<g256, 256, 0, st>>>(keys, vals, n, dcols, s->off.as<int64_t>(), s->nseg,
-                                            budget, ucount.as<int32_t>(), counts);
-    GD_HIP(hipGetLastError());
-    if (sorted) {
-        exclusive_scan_i32_to_i64(ctx, ucount.as<int32_t>(), ubase.as<int64_t>(), (size_t)n);
-        pairs_units_kernel<<<g256, 256, 0, st>>>(keys, n, ucount.as<int32_t>(), ubase.as<int64_t>(), s->nseg, ucap,
-                                                 units.as<int4>(), counts);
-        GD_HIP(hipGetLastError());
-        const unsigned grid = (unsigned)std::min<int64_t>(ucap, (int64_t)ctx->cus * 8);
-        pairs_sorted_kernel<<<grid, NTP, 0, st>>>(s->codes.as<uint64_t>(), s->segoff.as<int64_t>(), s->nseg, keys, vals,
-                                                  dcols, units.as<int4>(), counts, dI);
-        GD_HIP(hipGetLastError());
+        pl.plan_segment_units(s, codes);
+        const unsigned grid = (unsigned)std::min<int64_t>(pl.ucap, (int64_t)ctx->cus * 8);
+        pairs_sorted_kernel<<<grid, NTP, 0, st>>>(s->codes.as<uint64_t>(), s->segoff.as<int64_t>(), s->nseg, pl.keys,
+                                                  pl.vals, pl.cols, pl.units.as<int4>(), pl.counts, pl.I);
     } else {
+        pl.plan_groups();
         const bool rare = s->n_rare > 0;
         const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n, 4), (int64_t)ctx->cus * 16);
         pairs_bitset_kernel<<<grid, 256, 0, st>>>(
             s->bits.as<unsigned long long>(), s->W, rare ? s->srare_off.as<int64_t>() : nullptr,
             s->srare_ent.as<uint64_t>(), s->srare_w.as<uint32_t>(), s->post_sets.as<uint32_t>(),
             s->variant ? s->vs_off.as<int64_t>() : nullptr, s->vs_ent.as<uint32_t>(), s->vw_set.as<uint32_t>(),
-            s->vw_mask.as<unsigned long long>(), s->vw_beg.as<uint32_t>(), s->vw_end.as<uint32_t>(), keys, vals, dcols,
-            n, dI);
-        GD_HIP(hipGetLastError());
+            s->vw_mask.as<unsigned long long>(), s->vw_beg.as<uint32_t>(), s->vw_end.as<uint32_t>(), pl.keys, pl.vals,
+            pl.cols, n, pl.I);
     }
-    pairs_epilogue_kernel<<<g256, 256, 0, st>>>(s->off.as<int64_t>(), drows, dcols, n,
-                                                (flags & GDIST_EMPTY_NAN) ? 1 : 0, dI, dD);
     GD_HIP(hipGetLastError());
-    if (timed) GD_HIP(hipEventRecord(ev[1], st));
-    std::vector<char> hout(out_bytes);
-    d2h(hout.data(), dout.p, out_bytes, st);
-    if (timed) {
-        float ms = 0;
-        GD_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        ctx->pairs_kernel_ms = ms;
-    }
-    const auto* hc = reinterpret_cast<const unsigned long long*>(hout.data());
-    ctx->pairs_groups = (int64_t)hc[0];
-    ctx->pairs_units = sorted ? (int64_t)hc[1] : n;   // bitset path: a wave's worth of work a pair
-    if (I_out) std::memcpy(I_out, hout.data() + i_at, (size_t)n * 4);
-    if (D_out) std::memcpy(D_out, hout.data() + d_at, (size_t)n * 8);
+    pairs_epilogue_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(s->off.as<int64_t>(), pl.rows, pl.cols, n,
+                                                                      (flags & GDIST_EMPTY_NAN) ? 1 : 0, pl.I, pl.D);
+    GD_HIP(hipGetLastError());
+    pl.finish();
 }
 
 }  // namespace gdist

@@ -7,13 +7,10 @@
 // (WidthProcessor.java:183-192). The rectangle kernels do not fit: 10^5
 // scattered pairs among 50,000 sketches are 4e-5 of their bounding rectangle.
 //
-// Plan (on the device, as pairs.hip: one upload, no host round trip): the pair
-// positions are sorted by row (sort_pairs_u64_i32, stable: positions ascend
-// within a row); a run of equal row is a group, cut into units of at most
-// kSkpUnitPairs consecutive pairs (sketch_pairs_plan.hpp). A signature is at
-// most `width` hashes, so there is no code budget and a pair is never split.
-// skp_plan_kernel marks the unit heads and counts the groups, a scan places
-// the units, skp_units_kernel writes them; the merge kernel reads their number
+// Plan (PairList, pair_list.hip: one upload, no host round trip): the pair
+// positions sorted by row and cut into units of at most kPairUnit consecutive
+// pairs of one row. A signature is at most `width` hashes, so there is no code
+// budget and a pair is never split. The merge kernel reads the number of units
 // from device memory and strides over them.
 //
 // sketch_pairs_kernel: a workgroup of 16 waves takes units in a grid-stride
@@ -37,10 +34,7 @@
 // Lane 0 stores the pair's common count and / or distance at the pair's
 // original position: every position is in exactly one unit, so nothing is
 // zeroed and nothing at or past npairs is touched.
-#include <cstring>
-
 #include "gdist_internal.hpp"
-#include "sketch_pairs_plan.hpp"
 #include "sketch_wave_merge.hpp"
 
 namespace gdist {
@@ -56,35 +50,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__global__ void skp_keys_kernel(const int64_t* __restrict__ rows, int64_t n, uint64_t* __restrict__ keys,
-                                int32_t* __restrict__ vals) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    keys[p] = (uint64_t)rows[p];
-    vals[p] = (int32_t)p;
-}
-
-// counts[0] += the group heads; uhead[k] = 1 when sorted position k starts a unit
-__global__ void skp_plan_kernel(const uint64_t* __restrict__ keys, int64_t n, int32_t* __restrict__ uhead,
-                                unsigned long long* __restrict__ counts) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    if (skp_group_head(keys, k)) atomicAdd(&counts[0], 1ull);
-    uhead[k] = skp_unit_head(keys, k) ? 1 : 0;
-}
-
-// unit: {first sorted position, pairs}; counts[1] = the units
-__global__ void skp_units_kernel(const uint64_t* __restrict__ keys, int64_t n, const int32_t* __restrict__ uhead,
-                                 const int64_t* __restrict__ ubase, int2* __restrict__ units,
-                                 unsigned long long* __restrict__ counts) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const int u = uhead[k];
-    const int64_t b = ubase[k];
-    if (k == n - 1) counts[1] = (unsigned long long)(b + u);   // <= n: a unit holds a pair at least
-    if (u) units[b] = make_int2((int)k, skp_unit_pairs(keys, n, k));
 }
 
 // Rows index (asig, aoff), columns (bsig, boff). A workgroup holds up to
@@ -115,7 +80,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             const int64_t i = (int64_t)keys[un.x];
             const int64_t rb = aoff[i], rl = aoff[i + 1] - rb;
             s_k0[threadIdx.x] = un.x;
-            s_np[threadIdx.x] = un.y;                           // 1 .. kSkpUnitPairs
+            s_np[threadIdx.x] = un.y;                           // 1 .. kPairUnit
             s_rb[threadIdx.x] = rb;
             s_la[threadIdx.x] = (int)(rl < width ? rl : width);   // no signature is longer than the width
         }
@@ -173,51 +138,8 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 void sketch_pairs(gdist_ctx* ctx, const gdist_sets* a, const gdist_sets* b, unsigned flags, int64_t n,
                   const int64_t* rows, const int64_t* cols, int32_t* common_out, double* D_out) {
     hipStream_t st = ctx->stream;
-    const bool timed = ctx->option(OPT_TIME_KERNELS, 0) != 0;
-    ctx->pairs_kernel_ms = -1.0;
-    ctx->pairs_groups = ctx->pairs_units = 0;
-    // one upload: rows, then cols
-    std::vector<int64_t> hin((size_t)2 * n);
-    std::copy(rows, rows + n, hin.begin());
-    std::copy(cols, cols + n, hin.begin() + n);
-    DevBuf din((size_t)2 * n * 8, st);
-    DevBuf k0((size_t)n * 8, st), k1((size_t)n * 8, st), v0((size_t)n * 4, st), v1((size_t)n * 4, st);
-    DevBuf uhead((size_t)n * 4, st), ubase((size_t)n * 8, st), units((size_t)n * sizeof(int2), st);
-    // one download: {groups, units}, common, D
-    const size_t c_at = 16, d_at = c_at + (common_out ? ((size_t)n * 4 + 7) & ~(size_t)7 : 0);
-    const size_t out_bytes = d_at + (D_out ? (size_t)n * 8 : 0);
-    DevBuf dout(out_bytes, st);
-    auto* counts = dout.as<unsigned long long>();
-    int32_t* dC = common_out ? reinterpret_cast<int32_t*>(static_cast<char*>(dout.p) + c_at) : nullptr;
-    double* dD = D_out ? reinterpret_cast<double*>(static_cast<char*>(dout.p) + d_at) : nullptr;
-    const int64_t* drows = din.as<int64_t>();
-    const int64_t* dcols = drows + n;
-    h2d(din.p, hin.data(), (size_t)2 * n * 8, st);
-
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-    } guard{ev};
-    if (timed) {
-        for (auto& e : ev) GD_HIP(hipEventCreate(&e));
-        GD_HIP(hipEventRecord(ev[0], st));
-    }
-    const unsigned g256 = (unsigned)ceil_div(n, 256);
-    GD_HIP(hipMemsetAsync(dout.p, 0, c_at, st));           // the counts
-    uint64_t *keys = k0.as<uint64_t>(), *kalt = k1.as<uint64_t>();
-    int32_t *vals = v0.as<int32_t>(), *valt = v1.as<int32_t>();
-    skp_keys_kernel<<<g256, 256, 0, st>>>(drows, n, keys, vals);
-    GD_HIP(hipGetLastError());
-    int eb = 1;
-    while (eb < 64 && (int64_t(1) << eb) < a->nsets) eb++;
-    sort_pairs_u64_i32(ctx, keys, kalt, vals, valt, (size_t)n, 0, eb);
-    skp_plan_kernel<<<g256, 256, 0, st>>>(keys, n, uhead.as<int32_t>(), counts);
-    GD_HIP(hipGetLastError());
-    exclusive_scan_i32_to_i64(ctx, uhead.as<int32_t>(), ubase.as<int64_t>(), (size_t)n);
-    skp_units_kernel<<<g256, 256, 0, st>>>(keys, n, uhead.as<int32_t>(), ubase.as<int64_t>(), units.as<int2>(),
-                                           counts);
-    GD_HIP(hipGetLastError());
+    PairList pl(ctx, a->nsets, n, rows, cols, common_out, D_out, false);   // every position is stored once
+    pl.plan_units();
 
     const int width = std::max(1, a->width), sw = width | 1;
     // rows a step: what fits beside the 16 slices, at most kRows; none: the global variant
@@ -231,27 +153,15 @@ void sketch_pairs(gdist_ctx* ctx, const gdist_sets* a, const gdist_sets* b, unsi
         GD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    kLdsBytes));
         kern<<<grid, kNT, bytes, st>>>(a->codes.as<int32_t>(), a->off.as<int64_t>(), b->codes.as<int32_t>(),
-                                       b->off.as<int64_t>(), width, sw, nrows, keys, vals, dcols, units.as<int2>(),
-                                       counts, jaccard, empty_nan, dC, dD);
+                                       b->off.as<int64_t>(), width, sw, nrows, pl.keys, pl.vals, pl.cols,
+                                       pl.units.as<int2>(), pl.counts, jaccard, empty_nan, pl.I, pl.D);
     } else {
         sketch_pairs_kernel<false><<<grid, kNT, 0, st>>>(
             a->codes.as<int32_t>(), a->off.as<int64_t>(), b->codes.as<int32_t>(), b->off.as<int64_t>(), width, sw,
-            nrows, keys, vals, dcols, units.as<int2>(), counts, jaccard, empty_nan, dC, dD);
+            nrows, pl.keys, pl.vals, pl.cols, pl.units.as<int2>(), pl.counts, jaccard, empty_nan, pl.I, pl.D);
     }
     GD_HIP(hipGetLastError());
-    if (timed) GD_HIP(hipEventRecord(ev[1], st));
-    std::vector<char> hout(out_bytes);
-    d2h(hout.data(), dout.p, out_bytes, st);
-    if (timed) {
-        float ms = 0;
-        GD_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        ctx->pairs_kernel_ms = ms;
-    }
-    const auto* hc = reinterpret_cast<const unsigned long long*>(hout.data());
-    ctx->pairs_groups = (int64_t)hc[0];
-    ctx->pairs_units = (int64_t)hc[1];
-    if (common_out) std::memcpy(common_out, hout.data() + c_at, (size_t)n * 4);
-    if (D_out) std::memcpy(D_out, hout.data() + d_at, (size_t)n * 8);
+    pl.finish();
 }
 
 }  // namespace gdist

@@ -594,6 +594,31 @@ class _Handle:
 
     # the gdist_cross_* calls behind KmerSets.cross_* and SketchSets.cross_*: `queries` (rows) against this
     # resident collection (cols)
+    def _pairs(self, call, sets, rows, cols, args, want_I: bool, want_D: bool):
+        """A pair-list call (gdist_pairs, gdist_sketch_pairs): call(ctx, self,
+        *sets, n, rows, cols, *args, I, D) -> (I int32[P] | None, D float64[P] | None)."""
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        c = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
+        if len(r) != len(c):
+            raise ValueError(f"{len(r)} rows but {len(c)} cols")
+        n = len(r)
+        I = np.full(n, -1, dtype=np.int32) if want_I else None
+        D = np.full(n, np.nan, dtype=np.float64) if want_D else None
+        L.check(call(self.ctx.h, self.h, *sets, n, L.ptr(r, C.c_int64) if n else None,
+                     L.ptr(c, C.c_int64) if n else None, *args, L.ptr(I, C.c_int32) if want_I and n else None,
+                     L.ptr(D, C.c_double) if want_D and n else None))
+        return I, D
+
+    def pairs_info(self) -> tuple[float, int, int]:
+        """(kernel ms, groups, units) of the context's last pair-list call
+        (gdist_ctx_pairs_info): the kernel time is -1 unless option
+        time_kernels = 1; groups are the distinct rows of the list, units the
+        work units launched for them (sketches: the sum over the rows of
+        ceil(pairs of the row / 64))."""
+        ms, g, u = C.c_double(), C.c_int64(), C.c_int64()
+        L.check(L.lib.gdist_ctx_pairs_info(self.ctx.h, C.byref(ms), C.byref(g), C.byref(u)))
+        return ms.value, g.value, u.value
+
     def _cross_matrix(self, queries, rows, cols, flags: int, want_I: bool, want_D: bool):
         r0, r1 = rows or (0, len(queries))
         c0, c1 = cols or (0, len(self))
@@ -1053,27 +1078,7 @@ class KmerSets(_Handle):
         count and distance of sets (rows[p], cols[p]), in one device call:
         (I int32[P] | None, D float64[P] | None). Any order, repeats and i == j
         allowed; both are matrix()'s I and D of that cell bit for bit."""
-        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        c = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
-        if len(r) != len(c):
-            raise ValueError(f"{len(r)} rows but {len(c)} cols")
-        n = len(r)
-        I = np.full(n, -1, dtype=np.int32) if want_I else None
-        D = np.full(n, np.nan, dtype=np.float64) if want_D else None
-        L.check(L.lib.gdist_pairs(self.ctx.h, self.h, n, L.ptr(r, C.c_int64) if n else None,
-                                  L.ptr(c, C.c_int64) if n else None, method, flags,
-                                  L.ptr(I, C.c_int32) if want_I and n else None,
-                                  L.ptr(D, C.c_double) if want_D and n else None))
-        return I, D
-
-    def pairs_info(self) -> tuple[float, int, int]:
-        """(kernel ms, groups, units) of the context's last pairs() call
-        (gdist_ctx_pairs_info): the kernel time is -1 unless option
-        time_kernels = 1; groups are the distinct rows of the list, units the
-        work units launched for them."""
-        ms, g, u = C.c_double(), C.c_int64(), C.c_int64()
-        L.check(L.lib.gdist_ctx_pairs_info(self.ctx.h, C.byref(ms), C.byref(g), C.byref(u)))
-        return ms.value, g.value, u.value
+        return self._pairs(L.lib.gdist_pairs, (), rows, cols, (method, flags), want_I, want_D)
 
     def cross_matrix(self, queries: "KmerSets", rows: tuple[int, int] | None = None,
                      cols: tuple[int, int] | None = None, flags: int = 0, want_I: bool = True,
@@ -1336,27 +1341,7 @@ class SketchSets(_Handle):
         other.cross_matrix(self)'s cell (rows[p], cols[p]) bit for bit, with one
         collection matrix()'s. flags: SKETCH_JACCARD, EMPTY_NAN."""
         b = self if other is None else other
-        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        c = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
-        if len(r) != len(c):
-            raise ValueError(f"{len(r)} rows but {len(c)} cols")
-        n = len(r)
-        common = np.full(n, -1, dtype=np.int32) if want_common else None
-        D = np.full(n, np.nan, dtype=np.float64) if want_D else None
-        L.check(L.lib.gdist_sketch_pairs(self.ctx.h, self.h, b.h, n, L.ptr(r, C.c_int64) if n else None,
-                                         L.ptr(c, C.c_int64) if n else None, flags,
-                                         L.ptr(common, C.c_int32) if want_common and n else None,
-                                         L.ptr(D, C.c_double) if want_D and n else None))
-        return common, D
-
-    def pairs_info(self) -> tuple[float, int, int]:
-        """(kernel ms, groups, units) of the context's last pair-list call
-        (gdist_ctx_pairs_info): the kernel time is -1 unless option
-        time_kernels = 1; groups are the distinct rows of the list, units the
-        sum over them of ceil(pairs of the row / 64)."""
-        ms, g, u = C.c_double(), C.c_int64(), C.c_int64()
-        L.check(L.lib.gdist_ctx_pairs_info(self.ctx.h, C.byref(ms), C.byref(g), C.byref(u)))
-        return ms.value, g.value, u.value
+        return self._pairs(L.lib.gdist_sketch_pairs, (b.h,), rows, cols, (flags,), want_common, want_D)
 
     def row_query(self, q: int, cols: Iterable[int], mode: int = L.QUERY_ALL, t: float = 1.0,
                   other: "SketchSets | None" = None):

@@ -2,8 +2,9 @@
 parameter parsing, header and registry entry (gdist/methods.py), the host
 reduction SketchSets.row_query applies to a downloaded row of distances
 (gdist.kmers.reduce_row_query) against the plain Python rules of
-sketch_pairs_ref, and the unit cut of the plan (csrc/sketch_pairs_plan.hpp) in a
-stand-alone program with its own main under AddressSanitizer + UBSan."""
+sketch_pairs_ref, and the unit cut of the shared pair-list plan
+(csrc/pair_list.hpp: sketch chunks and the kmer cut by codes) in a stand-alone
+program with its own main under AddressSanitizer + UBSan."""
 import os
 import shutil
 import subprocess
@@ -108,14 +109,14 @@ def test_unit_count():
     assert R.unit_count(rows) == 38
 
 
-def test_sketch_pairs_plan_under_sanitizers(tmp_path):
+def test_pair_list_plan_under_sanitizers(tmp_path):
     cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
     if cxx is None:
         pytest.fail("no host C++ compiler on PATH")
-    exe = str(tmp_path / "sketch_pairs_check")
+    exe = str(tmp_path / "pair_list_check")
     subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "genome.distance_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "sketch_pairs_check.cpp"), "-o", exe], check=True)
+                    os.path.join(ROOT, "tests", "pair_list_check.cpp"), "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
     assert " 0 failures" in r.stdout, r.stdout[-2000:]
