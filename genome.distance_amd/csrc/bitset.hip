@@ -2630,6 +2630,7 @@ static MatrixPlan& matrix_plan(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, 
         if (s->plans.size() >= 8) {   // row-block loops: keep the cache small
             // launches on either stream may still read the old plans' buffers
             GD_HIP(hipStreamSynchronize(ctx->side));
+            GD_HIP(hipStreamSynchronize(ctx->tile2));
             GD_HIP(hipStreamSynchronize(ctx->stream));
             s->graphs.clear();        // (captured steps hold the plans' buffers)
             s->plans.clear();
@@ -2967,7 +2968,8 @@ void bitset_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
 }
 
 bool bitset_matrix_fused(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1,
-                         bool upper, unsigned flags, int32_t* d_I, int64_t ldI, double* d_D, int64_t ldD) {
+                         bool upper, unsigned flags, int32_t* d_I, int64_t ldI, double* d_D, int64_t ldD,
+                         bool pipelined) {
     // One stream, two launches: the sparse tile kernel (dense words folded
     // in) and its chunk reduce, which adds the rare pairs, STORES I (no
     // zeroing) and writes D (no epilogue launch). Only when every count of
@@ -2984,6 +2986,56 @@ bool bitset_matrix_fused(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_
     ep.off = s->off.as<int64_t>();
     ep.empty_nan = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
     hipStream_t st = ctx->stream;
+    if (pipelined) {
+        // Consecutive steps share nothing but the partials and the rare
+        // slab: with two copies of those, this step's tile launch goes to a
+        // stream of its own (the two tile streams turn about, so that two
+        // consecutive launches never queue behind each other) and fills the
+        // slots the previous launch's tail leaves idle, while the previous
+        // reduce runs beside it. The reduce stays on the context's stream,
+        // behind the event of its tile launch: outputs complete in that
+        // stream's order, and every tile launch so far has finished when
+        // this step's reduce runs, so whatever is ordered against the
+        // context's stream later (downloads, frees, rebuilds, other queries)
+        // is ordered against the tile streams too.
+        SparseScratch& sc = p.sparse;
+        if (!sparse_pipe_ready(ctx, sc)) return false;
+        const int64_t seq = ctx->api_seq.load();
+        SparsePipe pp;
+        pp.copy = (int)(sc.turn & 1);
+        const int ts = (int)(ctx->pipe_calls & 1);
+        pp.tile_st = ts ? ctx->tile2 : ctx->side;
+        pp.ev_tile = ctx->ev_tile[ts];
+        // The forward hazard: the tile launch must not pass work queued on
+        // the context's stream before this call. In an unbroken run of
+        // pipelined steps on one collection (the API entry before this one
+        // was such a step) a plan that already took a step of the run has
+        // nothing of its own on that stream but its reduces: the launch
+        // waits only for the reduce that last read the copy it overwrites,
+        // two of the plan's steps back. Anything else (the plan's first
+        // step of a run, another collection, any other call in between) is
+        // fully ordered behind the context's stream.
+        const bool run = ctx->pipe_sets == s && ctx->pipe_seq + 1 == seq;
+        if (!run) ctx->pipe_run0 = seq;
+        if (run && sc.pipe_seq >= ctx->pipe_run0) {
+            if (sc.ev_read_set[pp.copy]) GD_HIP(hipStreamWaitEvent(pp.tile_st, sc.ev_read[pp.copy], 0));
+        } else {
+            GD_HIP(hipEventRecord(ctx->ev_order, st));
+            GD_HIP(hipStreamWaitEvent(pp.tile_st, ctx->ev_order, 0));
+            ctx->n_pipe_ordered++;
+        }
+        sparse_matrix(ctx, s, r0, r1, c0, c1, upper, d_I, ldI, st, sc, &ep, &pp);
+        GD_HIP(hipEventRecord(sc.ev_read[pp.copy], st));
+        sc.ev_read_set[pp.copy] = true;
+        sc.turn++;
+        sc.pipe_seq = seq;
+        ctx->pipe_calls++;
+        ctx->pipe_seq = seq;
+        ctx->pipe_sets = s;
+        ctx->n_pipe++;
+        ctx->last.launches = 1;
+        return true;
+    }
     if (!ctx->capturing) GD_HIP(hipEventRecord(ctx->ev_k0, st));
     sparse_matrix(ctx, s, r0, r1, c0, c1, upper, d_I, ldI, st, p.sparse, &ep);
     if (!ctx->capturing) GD_HIP(hipEventRecord(ctx->ev_k1, st));

@@ -151,6 +151,9 @@ static int guard(F&& f) {
 static void use_device(gdist_ctx* ctx) {
     GD_REQUIRE(ctx != nullptr, "null context");
     GD_HIP(hipSetDevice(ctx->device));
+    // every API entry counts: a pipelined step is in an unbroken run only
+    // when the entry before it was one too (bitset.hip bitset_matrix_fused)
+    ctx->api_seq++;
 }
 
 static bool has_comm(const gdist_ctx* ctx) { return ctx->comm != nullptr || ctx->host_ag != nullptr; }
@@ -350,6 +353,10 @@ int gdist_ctx_create(int device, gdist_ctx** out) {
         c->ev_k0 = c->ring0[0];
         c->ev_k1 = c->ring1[0];
         GD_HIP(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+        GD_HIP(hipStreamCreateWithFlags(&c->tile2, hipStreamNonBlocking));
+        GD_HIP(hipEventCreateWithFlags(&c->ev_tile[0], hipEventDisableTiming));
+        GD_HIP(hipEventCreateWithFlags(&c->ev_tile[1], hipEventDisableTiming));
+        GD_HIP(hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming));
         GD_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
         GD_HIP(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
         for (int f = 0; f < gdist_ctx::kFamilies; f++) {
@@ -376,6 +383,11 @@ int gdist_ctx_destroy(gdist_ctx* ctx) {
             (void)hipEventDestroy(ctx->ring1[i]);
         }
         (void)hipStreamSynchronize(ctx->side);
+        (void)hipStreamSynchronize(ctx->tile2);
+        (void)hipEventDestroy(ctx->ev_tile[0]);
+        (void)hipEventDestroy(ctx->ev_tile[1]);
+        (void)hipEventDestroy(ctx->ev_order);
+        (void)hipStreamDestroy(ctx->tile2);
         (void)hipEventDestroy(ctx->ev_fork);
         (void)hipEventDestroy(ctx->ev_join);
         for (int f = 0; f < gdist_ctx::kFamilies; f++) {
@@ -405,6 +417,7 @@ int gdist_ctx_set_option(gdist_ctx* ctx, const char* name, int64_t value) {
         GD_REQUIRE(ctx, "null context");
         const int i = option_index(name);
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        ctx->api_seq++;
         ctx->opt[i] = value == GDIST_OPTION_DEFAULT ? kOptUnset : value;
         // launch plans cache per-call choices: drop none here (their keys
         // carry the options they depend on), sets built later see the value
@@ -705,6 +718,7 @@ int gdist_sets_free(gdist_sets* s) {
         if (!s) return;
         gdist_ctx* ctx = s->ctx;
         (void)hipSetDevice(ctx->device);
+        ctx->api_seq++;
         (void)hipStreamSynchronize(ctx->stream);
         delete s;   // stream-ordered frees
         (void)hipStreamSynchronize(ctx->stream);
@@ -1127,6 +1141,17 @@ int gdist_intersect_matrix(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, i
                 it = s->graphs.emplace(key, std::make_unique<StepGraph>()).first;
             }
             StepGraph& g = *it->second;
+            // A quiet fused sparse step goes out pipelined from the plan's
+            // second call on: direct launches, the tile kernel on one of two
+            // tile streams and the reduce on this stream, so that the next
+            // call's tile launch overlaps this call's tail and reduce
+            // (bitset_matrix_fused). Like a replayed step it records no
+            // timing events. Option serial_step = 1 keeps the one-stream
+            // graph replay below (the A/B switch).
+            if (quiet && D_out && g.calls >= 1 && !g.no_pipe && ctx->option(OPT_SERIAL_STEP, 0) == 0) {
+                if (bitset_matrix_fused(ctx, s, r0, r1, c0, c1, upper, flags, dI, ldI, D_out, ld, true)) return;
+                g.no_pipe = true;
+            }
             if (!g.exec && !g.failed && g.calls >= 1) {
                 hipGraph_t graph = nullptr;
                 GD_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -1151,6 +1176,7 @@ int gdist_intersect_matrix(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, i
                 if (!g.exec) g.failed = true;
             }
             if (g.exec) {
+                ctx->n_graph++;
                 if (quiet) {
                     GD_HIP(hipGraphLaunch(g.exec, st));
                     ctx->last.launches = 1;
@@ -1186,6 +1212,17 @@ int gdist_intersect_matrix(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, i
         if (D_out && !dev) copy_out_rows(ctx, dD, 8, nr, nc, r0, c0, upper, D_out, ld);
         if (I_out && !dev) copy_out_rows(ctx, dI, 4, nr, nc, r0, c0, upper, I_out, ld);
         gdist::finish_timing(ctx, true, dev);
+    });
+}
+
+int gdist_ctx_step_info(gdist_ctx* ctx, int64_t out[4]) {
+    return guard([&] {
+        GD_REQUIRE(ctx != nullptr && out != nullptr, "null argument");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        out[0] = ctx->n_pipe;
+        out[1] = ctx->n_pipe_ordered;
+        out[2] = ctx->n_graph;
+        out[3] = ctx->pipe_bytes;
     });
 }
 
@@ -1385,6 +1422,7 @@ int gdist_lsh_free(gdist_lsh* lsh) {
     return guard([&] {
         if (!lsh) return;
         (void)hipSetDevice(lsh->ctx->device);
+        lsh->ctx->api_seq++;
         delete lsh;
     });
 }

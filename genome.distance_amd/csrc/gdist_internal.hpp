@@ -8,6 +8,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <functional>
 #include <cstdint>
@@ -152,6 +153,36 @@ struct SparseScratch {
     int nchunks = 0;         // chunks of an off-diagonal tile (the most any tile has)
     bool use_part = false;   // chunks store partials (else flush with atomics)
     int64_t ntiles = 0;
+    // Pipelined steps (bitset_matrix_fused): `part` and
+    // `rare_slab` are the only buffers the tile launch writes and the reduce
+    // reads, so a second copy of the two, taken turn about, lets the next
+    // call's tile launch run beside this call's reduce. Behind each copy's
+    // last reduce an event: the next tile launch into that copy waits on it.
+    // Allocated when pipelining is first asked for and both copies of the
+    // partials fit option sparse_part_budget (sparse.hip sparse_pipe_ready).
+    DevBuf part2, rare_slab2;
+    bool pipe_tried = false, pipe = false;
+    int64_t turn = 0;             // pipelined steps so far: the next writes copy turn & 1
+    int64_t pipe_seq = -1;        // the context's API sequence number at this plan's last pipelined step
+    hipEvent_t ev_read[2] = {nullptr, nullptr};
+    bool ev_read_set[2] = {false, false};
+    int64_t* held = nullptr;      // the context's count of second-copy bytes (gdist_ctx_step_info)
+    SparseScratch() = default;
+    SparseScratch(const SparseScratch&) = delete;
+    SparseScratch& operator=(const SparseScratch&) = delete;
+    ~SparseScratch() {
+        for (hipEvent_t e : ev_read)
+            if (e) (void)hipEventDestroy(e);
+        if (held) *held -= (int64_t)(part2.bytes + rare_slab2.bytes);
+    }
+};
+// The streams and the copy of one pipelined step (sparse_matrix): the tile
+// launch goes to `tile_st`, `ev_tile` is recorded behind it, and the reduce
+// on the caller's stream waits on that event.
+struct SparsePipe {
+    int copy = 0;
+    hipStream_t tile_st = nullptr;
+    hipEvent_t ev_tile = nullptr;
 };
 // One captured step: zero counts, the tile / sparse / rare launches on both
 // streams, the epilogue (gdist_intersect_matrix, option graph)
@@ -159,6 +190,7 @@ struct StepGraph {
     hipGraphExec_t exec = nullptr;
     int calls = 0;          // uncaptured calls so far (the first builds the launch plans)
     bool failed = false;    // capture refused: this key runs uncaptured
+    bool no_pipe = false;   // the step cannot be pipelined (not fused, or no room for the second copies)
     ~StepGraph() { if (exec) (void)hipGraphExecDestroy(exec); }
 };
 struct MatrixPlan {
@@ -318,6 +350,23 @@ struct gdist_ctx {
     size_t pinned_bytes = 0;
     hipEvent_t ev_stage[2] = {nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // Pipelined fused sparse steps (bitset_matrix_fused): tile launches turn
+    // about on `side` and `tile2`, every reduce on `stream`. Three streams in
+    // all; a context opens no more.
+    hipStream_t tile2 = nullptr;
+    hipEvent_t ev_tile[2] = {nullptr, nullptr};   // behind the last tile launch of each tile stream
+    hipEvent_t ev_order = nullptr;                // a fully ordered step: everything on `stream` so far
+    // every API entry on this context bumps api_seq (use_device): a step is
+    // in an unbroken run of pipelined steps when the entry before it was one,
+    // on the same collection
+    std::atomic<int64_t> api_seq{0};
+    int64_t pipe_seq = -1;                        // api_seq of the last pipelined step
+    int64_t pipe_run0 = 0;                        // api_seq of the first step of the current run
+    const gdist_sets* pipe_sets = nullptr;        // its collection
+    int64_t pipe_calls = 0;                       // pipelined steps: the next tile launch goes to stream pipe_calls & 1
+    // gdist_ctx_step_info: steps on the three streams, those of them fully
+    // ordered, steps replayed as a graph, bytes of second buffer copies
+    int64_t n_pipe = 0, n_pipe_ordered = 0, n_graph = 0, pipe_bytes = 0;
     // option time_kernels: each kernel family's launches alone (uncaptured
     // calls), by family (GDIST_KERNEL_SPARSE / RARE / DENSE / SORTED)
     static constexpr int kFamilies = 5;
@@ -591,9 +640,13 @@ void build_bitsets(gdist_ctx* ctx, gdist_sets* s, unsigned flags, int64_t rare_t
 void bitset_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, int64_t c0,
                    int64_t c1, bool upper, int32_t* d_I, int64_t ldI);
 // the fused sparse step (sparse tiles + reduce storing I and D): true when it
-// ran, false when the region needs zeroing + bitset_matrix + epilogue
+// ran, false when the region needs zeroing + bitset_matrix + epilogue.
+// pipelined: the tile launch on one of the two tile streams, into the plan's
+// next buffer copy, and the reduce on the context's stream behind it; false
+// (nothing launched) also when the plan has no room for its second copies
 bool bitset_matrix_fused(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1,
-                         bool upper, unsigned flags, int32_t* d_I, int64_t ldI, double* d_D, int64_t ldD);
+                         bool upper, unsigned flags, int32_t* d_I, int64_t ldI, double* d_D, int64_t ldD,
+                         bool pipelined = false);
 
 // sparse.hip — locus order of the dense dictionary, complement-sparse words
 constexpr int kGuides = 8;                       // guide sequences per packed collection (C2-realistic, 8
@@ -626,7 +679,12 @@ void sparse_plan(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, in
                  hipStream_t st, SparseScratch& sc);
 // returns true when the rare tier's pairs were added with the sparse words
 bool sparse_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, bool upper,
-                   int32_t* d_I, int64_t ldI, hipStream_t st, SparseScratch& sc, const SparseEpilogue* ep = nullptr);
+                   int32_t* d_I, int64_t ldI, hipStream_t st, SparseScratch& sc, const SparseEpilogue* ep = nullptr,
+                   const SparsePipe* pp = nullptr);
+// true when the plan's steps may be pipelined: allocates the second copies of
+// the partials and the rare slab the first time it is asked (a built plan
+// with partials whose two copies fit option sparse_part_budget)
+bool sparse_pipe_ready(gdist_ctx* ctx, SparseScratch& sc);
 
 // The bitset build of a replicated collection split by rank (option
 // split_build): share r counts the code ranges [Pe r / R, Pe (r + 1) / R) of

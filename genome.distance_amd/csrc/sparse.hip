@@ -1250,6 +1250,7 @@ bool locus_order_enabled(const gdist_ctx* ctx) { return ctx->option(OPT_LOCUS_OR
 void free_sparse(gdist_sets* s) {
     if (s->ctx) {                        // launches on the side stream may still read these buffers
         (void)hipStreamSynchronize(s->ctx->side);
+        (void)hipStreamSynchronize(s->ctx->tile2);
         (void)hipStreamSynchronize(s->ctx->stream);
     }
     s->fp4.release();                     // the MFMA operand expands the dense words
@@ -1929,12 +1930,41 @@ GroupPart group_part(const gdist_sets* s) {
     return g;
 }
 
+bool sparse_pipe_ready(gdist_ctx* ctx, SparseScratch& sc) {
+    if (sc.pipe_tried || !sc.ready) return sc.pipe;
+    sc.pipe_tried = true;
+    const int64_t budget = ctx->option(OPT_SPARSE_PART_BUDGET, int64_t(1) << 30);
+    if (!sc.use_part || 2 * (int64_t)sc.part.bytes > budget) return false;
+    try {
+        for (hipEvent_t& e : sc.ev_read) GD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        sc.part2.alloc(sc.part.bytes, ctx->stream);
+        if (sc.rare_in) sc.rare_slab2.alloc(sc.rare_slab.bytes, ctx->stream);
+    } catch (const Error& e) {
+        if (e.code != GDIST_ENOMEM) throw;
+        (void)hipGetLastError();          // no room beside the collection: the plan stays unpipelined
+        sc.part2.release();
+        sc.rare_slab2.release();
+        return false;
+    }
+    sc.held = &ctx->pipe_bytes;
+    *sc.held += (int64_t)(sc.part2.bytes + sc.rare_slab2.bytes);
+    sc.pipe = true;
+    return true;
+}
+
 bool sparse_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, bool upper,
-                   int32_t* d_I, int64_t ldI, hipStream_t st, SparseScratch& sc, const SparseEpilogue* ep) {
+                   int32_t* d_I, int64_t ldI, hipStream_t st, SparseScratch& sc, const SparseEpilogue* ep,
+                   const SparsePipe* pp) {
     if (!s->sparse || r1 <= r0 || c1 <= c0) return false;
     sparse_plan(ctx, s, r0, r1, c0, c1, upper, st, sc);
     GD_REQUIRE(!ep || (sc.use_part && (s->n_rare == 0 || sc.rare_in)), "fused sparse epilogue without its plan");
+    GD_REQUIRE(!pp || (ep && sc.pipe), "pipelined sparse step without its buffer copies");
     if (sc.ntiles == 0) return false;
+    // a pipelined step: the tile launch on its own stream into the step's
+    // copy of the partials and the slab, the reduce on `st` behind it
+    hipStream_t tst = pp ? pp->tile_st : st;
+    const DevBuf& part = pp && pp->copy ? sc.part2 : sc.part;
+    const DevBuf& rare_slab = pp && pp->copy ? sc.rare_slab2 : sc.rare_slab;
     const int nchunks = sc.nchunks;
     const int64_t nt = sc.ntiles;
     // __launch_bounds__'s second argument is the minimum waves per SIMD: 8
@@ -1952,7 +1982,7 @@ bool sparse_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
                         : (sun == 2 ? sparse_tile_kernel<2, 1> : sun == 4 ? sparse_tile_kernel<4, 1> : sparse_tile_kernel<3, 1>);
     // the rare tier's pairs of this step: the launch's trailing workgroups
     const bool rare = sc.use_part && sc.rare_in;
-    FamilyTimer ft(ctx, GDIST_KERNEL_SPARSE, st);
+    FamilyTimer ft(ctx, GDIST_KERNEL_SPARSE, tst);
     const bool xmap = ctx->option(OPT_SPARSE_XCD, 0) != 0;
     RareSlab rs;
     if (rare) {
@@ -1961,17 +1991,17 @@ bool sparse_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
         const int64_t nrare = (r1 - r0) * rs.nch;
         GD_REQUIRE(nrare < (int64_t(1) << 30), "too many rare rows");
         rs.nrare = (int)nrare;
-        rs.slab = sc.rare_slab.as<uint32_t>();
+        rs.slab = rare_slab.as<uint32_t>();
         rs.tile_of = sc.rare_tile.as<int32_t>();
         rs.ab0 = sc.rare_ab0;
         rs.nbc = sc.rare_nbc;
     }
     const int64_t grid = (xmap ? ceil_div(nchunks, 8) * 8 * nt : sc.total_chunks) + rs.nrare;
     GD_REQUIRE(grid < (int64_t(1) << 31), "sparse grid too large");
-    kern<<<(unsigned)grid, SNT, 0, st>>>(s->sp_off.as<int64_t>(), s->sp_ent.as<ulonglong2>(), s->sp_nc.as<int32_t>(),
+    kern<<<(unsigned)grid, SNT, 0, tst>>>(s->sp_off.as<int64_t>(), s->sp_ent.as<ulonglong2>(), s->sp_nc.as<int32_t>(),
                                          s->sp_U, s->Ws, sc.tiles.as<int2>(), sc.bounds.as<int32_t>(),
                                          sc.tinfo.as<int4>(), sc.wgmap.as<int2>(), nchunks, r0, r1,
-                                         c0, c1, upper ? 1 : 0, d_I, ldI, sc.use_part ? sc.part.as<int32_t>() : nullptr,
+                                         c0, c1, upper ? 1 : 0, d_I, ldI, sc.use_part ? part.as<int32_t>() : nullptr,
                                          s->Wd, s->nsets, s->dbits.as<unsigned long long>(), s->sp_fold_slabs,
                                          group_part(s), xmap ? 1 : 0, (int)nt, rs,
                                          (int)ctx->option(OPT_SPARSE_DYN, 1), (int)ctx->option(OPT_SPARSE_DIAG22, 1),
@@ -1979,12 +2009,16 @@ bool sparse_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
                                          (int)ctx->option(OPT_SPARSE_WTAIL, 1));
     GD_HIP(hipGetLastError());
     ft.end();
+    if (pp) {
+        GD_HIP(hipEventRecord(pp->ev_tile, tst));
+        GD_HIP(hipStreamWaitEvent(st, pp->ev_tile, 0));
+    }
     if (sc.use_part) {
         sparse_reduce_kernel<<<(unsigned)(nt * (SB * SB / kReduceCnt / kReduceGroups)), 256, 0, st>>>(
-            sc.part.as<int32_t>(), sc.tinfo.as<int4>(), sc.tiles.as<int2>(), s->sp_nc.as<int32_t>(), s->sp_U, r0, r1,
+            part.as<int32_t>(), sc.tinfo.as<int4>(), sc.tiles.as<int2>(), s->sp_nc.as<int32_t>(), s->sp_U, r0, r1,
             c0, c1,
             upper ? 1 : 0, d_I, ldI,
-            rare ? sc.rare_slab.as<uint32_t>() : nullptr, ep ? ep->D : nullptr, ep ? ep->ldD : 0,
+            rare ? rare_slab.as<uint32_t>() : nullptr, ep ? ep->D : nullptr, ep ? ep->ldD : 0,
             ep ? ep->off : nullptr, ep ? ep->empty_nan : 0, group_part(s));
         GD_HIP(hipGetLastError());
     }

@@ -170,6 +170,7 @@ _SIGS = {
     "gdist_cross_histogram": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64, _i64, _i64, _u32, C.c_int, _dblp, C.c_int,
                                         _i32p, _i32p, _i64p, _i64p, _i64p]),
     "gdist_ctx_cross_info": (C.c_int, [_ctxp, _dblp, _dblp, _i64p]),
+    "gdist_ctx_step_info": (C.c_int, [_ctxp, _i64p]),
     "gdist_histogram": (C.c_int, [_ctxp, _setp, _i64, _i64, _i64, _i64, C.c_int, _u32, C.c_int, _dblp, C.c_int, _i32p,
                                   _i64p, _i64p, _i64p]),
     "gdist_ctx_histogram_timing": (C.c_int, [_ctxp, _dblp, _dblp]),

@@ -161,6 +161,15 @@ class Context:
         L.check(L.lib.gdist_ctx_cross_info(self.h, C.byref(j), C.byref(s), C.byref(u)))
         return j.value, s.value, u.value
 
+    def step_info(self) -> tuple[int, int, int, int]:
+        """How the context's repeated matrix_device() calls went out so far
+        (gdist_ctx_step_info): (fused sparse steps issued pipelined over the
+        three streams, those of them fully ordered behind the context's stream
+        first, steps replayed as one graph, bytes of second buffer copies held)."""
+        out = (C.c_int64 * 4)()
+        L.check(L.lib.gdist_ctx_step_info(self.h, out))
+        return tuple(int(x) for x in out)
+
     def recent_timings(self, n: int) -> list[float]:
         """Kernel ms of the last n matrix calls, oldest first (waits for them)."""
         out = np.zeros(max(n, 1), dtype=np.float64)

@@ -343,11 +343,28 @@ int  gdist_sets_prepare(gdist_ctx* ctx, gdist_sets* sets, int method, double pai
 /* Pairs (i, j), r0 <= i < r1, c0 <= j < c1 (global set indices of `sets`).
  * I_out[(i-r0)*ld + (j-c0)] = |A_i ∩ A_j|, D_out[...] = distance; either
  * output may be NULL. With GDIST_UPPER_TRIANGLE, entries with j <= i are
- * left untouched. */
+ * left untouched.
+ * Ordering of device outputs (GDIST_OUT_DEVICE): a call's I_out and D_out are
+ * complete in the order of the context's stream, whatever streams the library
+ * launched on (repeated fused sparse steps run their tile kernels on two
+ * further streams so that consecutive calls overlap; each call's reduce, the
+ * only writer of its outputs, stays on the context's stream). Every later
+ * call on the context (a download, another query, a free, a rebuild) is
+ * ordered behind them, gdist_ctx_synchronize waits for them, and consecutive
+ * calls may share output buffers: they are written in call order. */
 int  gdist_intersect_matrix(gdist_ctx* ctx, const gdist_sets* sets,
                             int64_t r0, int64_t r1, int64_t c0, int64_t c1,
                             int method, unsigned flags,
                             int32_t* I_out, double* D_out, int64_t ld);
+/* How the context's repeated gdist_intersect_matrix calls into device outputs
+ * went out so far: out[0] fused sparse steps issued pipelined (tile launch on
+ * a tile stream, reduce on the context's stream), out[1] those of them that
+ * were fully ordered behind the context's stream first (a plan's first step
+ * of a run, another collection, or any other API call in between), out[2]
+ * steps replayed as one hipGraph on the context's stream (every step under
+ * option "serial_step" = 1), out[3] bytes of second buffer copies (chunk
+ * partials, rare slab) the pipelined plans hold. */
+int  gdist_ctx_step_info(gdist_ctx* ctx, int64_t out[4]);
 /* Greedy representatives over the whole collection, on the device.
  * Pass 1 (DistanceRepsProcessor.java:185-200, FastaDistanceRepsProcessor.java:
  * 117-144): sets in index order; set k becomes a representative unless an
