@@ -1725,6 +1725,26 @@ int gdist_cross_matrix(gdist_ctx* ctx, const gdist_sets* queries, const gdist_se
     });
 }
 
+// the pair list of the cross calls: reports through gdist_ctx_pairs_info, as the
+// other pair-list calls do (gdist_ctx_cross_info keeps the last walk's figures)
+int gdist_cross_pairs(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects, int64_t npairs,
+                      const int64_t* rows, const int64_t* cols, unsigned flags, int32_t* I_out, double* D_out) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_cross(ctx, queries, subjects, 0, 0, 0, 0, flags);
+        begin_pairs(ctx, npairs, rows, queries->nsets, "row index outside the query collection", cols,
+                    subjects->nsets, "column index outside the subject collection", I_out, D_out);
+        if (npairs == 0) return;
+        auto* s = const_cast<gdist_sets*>(subjects);
+        begin_call(ctx);
+        if (queries->kind == GDIST_SKETCH)
+            return gdist::sketch_pairs(ctx, queries, s, flags, npairs, rows, cols, I_out, D_out);
+        cross_index(ctx, s);
+        gdist::cross_pairs(ctx, queries, s, flags, npairs, rows, cols, I_out, D_out);
+    });
+}
+
 int gdist_cross_closest(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects, int64_t q0, int64_t q1,
                         int64_t c0, int64_t c1, unsigned flags, int n, double max_dist, int64_t* idx_out,
                         double* d_out, int32_t* count_out) {

@@ -1008,9 +1008,10 @@ struct PairList {
     ~PairList();
     void plan_groups();                // no units: a pair is a unit of work
     void plan_units();                 // int2 {first sorted position, pairs}: a chunk
-    // int4 {first sorted position, pairs, first segment, end segment}: a chunk of the
-    // collection s cut by its codes; codes: the list's, over its pairs, both sets
-    void plan_segment_units(const gdist_sets* s, double codes);
+    // int4 {first sorted position, pairs, first segment, end segment}: a chunk cut by
+    // its codes into ranges of s's segment index; the rows index r, the columns s
+    // (gdist_pairs: the same collection); codes: the list's, over its pairs, both sets
+    void plan_segment_units(const gdist_sets* r, const gdist_sets* s, double codes);
     void finish();
 
     DevBuf in, k0, k1, v0, v1, ucount, ubase, out;
@@ -1026,6 +1027,13 @@ struct PairList {
 // rows / cols / I_out / D_out: host, n entries, either output may be null
 void pairs(gdist_ctx* ctx, const gdist_sets* s, int method, unsigned flags, int64_t n, const int64_t* rows,
            const int64_t* cols, int32_t* I_out, double* D_out);
+
+// cross_pairs.hip — a pair list across two collections of kmer sets (gdist_cross_pairs)
+// every argument checked by the caller, n > 0, the subjects' segment index
+// built; rows index q, cols index s; rows / cols / I_out / D_out: host, n
+// entries, either output may be null
+void cross_pairs(gdist_ctx* ctx, const gdist_sets* q, const gdist_sets* s, unsigned flags, int64_t n,
+                 const int64_t* rows, const int64_t* cols, int32_t* I_out, double* D_out);
 
 // sketch_pairs.hip — the sketch distances of a pair list (gdist_sketch_pairs)
 // every argument checked by the caller, n > 0; rows index a, cols index b;

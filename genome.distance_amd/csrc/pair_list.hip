@@ -1,5 +1,6 @@
 // pair_list.hip — the plan of a pair list on the device (struct PairList,
-// gdist_internal.hpp): what gdist_pairs and gdist_sketch_pairs do alike.
+// gdist_internal.hpp): what gdist_pairs, gdist_cross_pairs and
+// gdist_sketch_pairs do alike.
 //
 // The pair positions are sorted by row (sort_pairs_u64_i32, stable: positions
 // ascend within a row); the runs of equal row are the groups, cut into chunks
@@ -23,19 +24,20 @@ struct ChunkCut {
     __device__ int2 unit(int k, int c, int, int) const { return make_int2(k, c); }
 };
 
-// a chunk whose codes exceed the budget is cut into ranges of the segment index
+// a chunk whose codes exceed the budget is cut into ranges of the segment index;
+// the row's size from roff, the columns' from coff (one collection: the same)
 struct SegmentCut {
     using Unit = int4;
-    const int64_t *cols, *off;
+    const int64_t *cols, *roff, *coff;
     int nseg;
     int64_t budget;
     __device__ int units(const uint64_t* keys, const int32_t* vals, int64_t n, int64_t k) const {
         const uint64_t key = keys[k];
         const int c = pl_unit_pairs(keys, n, k);
-        int64_t codes = off[key + 1] - off[key];
+        int64_t codes = roff[key + 1] - roff[key];
         for (int t = 0; t < c; t++) {
             const int64_t j = cols[vals[k + t]];
-            codes += off[j + 1] - off[j];
+            codes += coff[j + 1] - coff[j];
         }
         return pl_chunk_units(codes, budget, nseg);
     }
@@ -151,9 +153,10 @@ void PairList::plan_groups() { plan(*this, ChunkCut{}, 0); }
 
 void PairList::plan_units() { plan(*this, ChunkCut{}, n); }   // a chunk holds a pair at least
 
-void PairList::plan_segment_units(const gdist_sets* s, double codes) {
+void PairList::plan_segment_units(const gdist_sets* r, const gdist_sets* s, double codes) {
     const int64_t budget = pl_budget(codes, ctx->cus);
-    plan(*this, SegmentCut{cols, s->off.as<int64_t>(), s->nseg, budget}, pl_unit_cap(n, codes, budget));
+    plan(*this, SegmentCut{cols, r->off.as<int64_t>(), s->off.as<int64_t>(), s->nseg, budget},
+         pl_unit_cap(n, codes, budget));
 }
 
 void PairList::finish() {

@@ -196,7 +196,7 @@ void pairs(gdist_ctx* ctx, const gdist_sets* s, int method, unsigned flags, int6
         double codes = 0;
         for (int64_t p = 0; p < n; p++)
             codes += (double)(s->h_off[rows[p] + 1] - s->h_off[rows[p]] + s->h_off[cols[p] + 1] - s->h_off[cols[p]]);
-        pl.plan_segment_units(s, codes);
+        pl.plan_segment_units(s, s, codes);
         const unsigned grid = (unsigned)std::min<int64_t>(pl.ucap, (int64_t)ctx->cus * 8);
         pairs_sorted_kernel<<<grid, NTP, 0, st>>>(s->codes.as<uint64_t>(), s->segoff.as<int64_t>(), s->nseg, pl.keys,
                                                   pl.vals, pl.cols, pl.units.as<int4>(), pl.counts, pl.I);

@@ -60,14 +60,16 @@ def tree_source_hash() -> str:
     """sha256 prefix of the library's sources in this tree, in the Makefile's
     order (csrc/*.hip by name, csrc/gdist_internal.hpp, csrc/sparse_bounds.hpp,
     csrc/group_stats_host.hpp, csrc/cross_plan.hpp, csrc/sketch_cross_merge.hpp,
-    csrc/sketch_wave_merge.hpp, csrc/pair_list.hpp, include/gdist.h)."""
+    csrc/sketch_wave_merge.hpp, csrc/pair_list.hpp, csrc/cross_cut.hpp,
+    include/gdist.h)."""
     import glob
     import hashlib
     files = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hip")))
     files += [os.path.join(_PKG, "csrc", "gdist_internal.hpp"), os.path.join(_PKG, "csrc", "sparse_bounds.hpp"),
               os.path.join(_PKG, "csrc", "group_stats_host.hpp"), os.path.join(_PKG, "csrc", "cross_plan.hpp"),
               os.path.join(_PKG, "csrc", "sketch_cross_merge.hpp"), os.path.join(_PKG, "csrc", "sketch_wave_merge.hpp"),
-              os.path.join(_PKG, "csrc", "pair_list.hpp"), os.path.join(_REPO, "include", "gdist.h")]
+              os.path.join(_PKG, "csrc", "pair_list.hpp"), os.path.join(_PKG, "csrc", "cross_cut.hpp"),
+              os.path.join(_REPO, "include", "gdist.h")]
     h = hashlib.sha256()
     for f in files:
         with open(f, "rb") as fh:
@@ -161,6 +163,7 @@ _SIGS = {
     "gdist_pairs": (C.c_int, [_ctxp, _setp, _i64, _i64p, _i64p, C.c_int, _u32, _i32p, _dblp]),
     "gdist_ctx_pairs_info": (C.c_int, [_ctxp, _dblp, _i64p, _i64p]),
     "gdist_cross_matrix": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64, _i64, _i64, _u32, _i32p, _dblp, _i64]),
+    "gdist_cross_pairs": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64p, _i64p, _u32, _i32p, _dblp]),
     "gdist_cross_closest": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64, _i64, _i64, _u32, C.c_int, _dbl, _i64p, _dblp,
                                       _i32p]),
     "gdist_cross_within": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64, _i64, _i64, _u32, _dbl, _i64, _i64p, _i64p, _dblp,

@@ -604,7 +604,7 @@ class _Handle:
     # the gdist_cross_* calls behind KmerSets.cross_* and SketchSets.cross_*: `queries` (rows) against this
     # resident collection (cols)
     def _pairs(self, call, sets, rows, cols, args, want_I: bool, want_D: bool):
-        """A pair-list call (gdist_pairs, gdist_sketch_pairs): call(ctx, self,
+        """A pair-list call (gdist_pairs, gdist_cross_pairs, gdist_sketch_pairs): call(ctx, self,
         *sets, n, rows, cols, *args, I, D) -> (I int32[P] | None, D float64[P] | None)."""
         r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
         c = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
@@ -1082,12 +1082,22 @@ class KmerSets(_Handle):
         return self._quantiles(q, rows, cols, upper, method, flags)
 
     def pairs(self, rows, cols, method: int = L.METHOD_AUTO, flags: int = 0, want_I: bool = True,
-              want_D: bool = True):
+              want_D: bool = True, *, other: "KmerSets | None" = None):
         """Distances of a pair list (gdist_pairs): for every p the intersection
         count and distance of sets (rows[p], cols[p]), in one device call:
         (I int32[P] | None, D float64[P] | None). Any order, repeats and i == j
-        allowed; both are matrix()'s I and D of that cell bit for bit."""
-        return self._pairs(L.lib.gdist_pairs, (), rows, cols, (method, flags), want_I, want_D)
+        allowed; both are matrix()'s I and D of that cell bit for bit.
+
+        With `other` (gdist_cross_pairs) rows index this collection (the
+        queries) and cols index `other` (the resident subjects, only read):
+        other.cross_matrix(self)'s cell (rows[p], cols[p]) bit for bit. There
+        is no bitset route across two collections: method must be AUTO or
+        SORTED; flags: EMPTY_NAN or 0."""
+        if other is None:
+            return self._pairs(L.lib.gdist_pairs, (), rows, cols, (method, flags), want_I, want_D)
+        if method not in (L.METHOD_AUTO, L.METHOD_SORTED):
+            raise ValueError("a pair list across two collections runs the sorted join: method AUTO or SORTED")
+        return self._pairs(L.lib.gdist_cross_pairs, (other.h,), rows, cols, (flags,), want_I, want_D)
 
     def cross_matrix(self, queries: "KmerSets", rows: tuple[int, int] | None = None,
                      cols: tuple[int, int] | None = None, flags: int = 0, want_I: bool = True,
@@ -1185,17 +1195,16 @@ class SequenceKmers:
         """SequenceKmers.distance(other) — FastaDistanceProcessor.java:186."""
         if other.sets is self.sets:
             return float(self.sets.row_query(self.index, [other.index])[0])
-        both = self.sets.concat(other.sets)
-        return float(both.row_query(self.index, [len(self.sets) + other.index])[0])
+        # one cell against the other collection as it is: no copy of either (gdist_cross_pairs)
+        _, D = self.sets.pairs([self.index], [other.index], want_I=False, other=other.sets)
+        return float(D[0])
 
     def similarity(self, other: "SequenceKmers") -> int:
         if other.sets is self.sets:
             I, _ = self.sets.matrix((self.index, self.index + 1), (other.index, other.index + 1), want_D=False)
             return int(I[0, 0])
-        both = self.sets.concat(other.sets)
-        j = len(self.sets) + other.index
-        I, _ = both.matrix((self.index, self.index + 1), (j, j + 1), want_D=False)
-        return int(I[0, 0])
+        I, _ = self.sets.pairs([self.index], [other.index], want_D=False, other=other.sets)
+        return int(I[0])
 
     def hashSet(self, width: int) -> np.ndarray:
         """SequenceKmers.hashSet(width) — SketchProcessor.java:88."""

@@ -39,6 +39,8 @@
  *                          against the loaded genome database    FindProcessor.java:94-110, MashProcessor.java:150
  *   gdist_cross_matrix     the same queries x database rectangle
  *                          as counts and distances               GenomeProcessor.java:140
+ *   gdist_cross_pairs      getDistance over an (id1, id2) list of
+ *                          new genomes x database genomes        MethodTableProcessor.java:258-276
  *   gdist_cross_within     the -m filter of comparison genomes
  *                          against the pre-loaded base genomes   GenomeProcessor.java:35,140
  *   gdist_cross_group_stats in / out-group summary of new genomes
@@ -608,7 +610,7 @@ int  gdist_ctx_within_timing(gdist_ctx* ctx, double* matrix_ms, double* select_m
 int  gdist_pairs(gdist_ctx* ctx, const gdist_sets* sets, int64_t npairs,
                  const int64_t* rows, const int64_t* cols, int method, unsigned flags,
                  int32_t* I_out, double* D_out);
-/* last gdist_pairs or gdist_sketch_pairs call: kernel time (ms; -1 unless option "time_kernels" = 1), the
+/* last gdist_pairs, gdist_cross_pairs or gdist_sketch_pairs call: kernel time (ms; -1 unless option "time_kernels" = 1), the
  * distinct-row groups of the list and the work units launched for them */
 int  gdist_ctx_pairs_info(gdist_ctx* ctx, double* kernel_ms, int64_t* groups, int64_t* units);
 
@@ -691,6 +693,53 @@ int  gdist_cross_closest(gdist_ctx* ctx, const gdist_sets* queries, const gdist_
                          int64_t q0, int64_t q1, int64_t c0, int64_t c1, unsigned flags,
                          int n, double max_dist,
                          int64_t* idx_out, double* d_out, int32_t* count_out);
+
+/* gdist_cross_pairs: getDistance over a pair list (MethodTableProcessor.java:258-276;
+ * the lists BasicPairsProcessor.java:71-89 and PairCreateProcessor.java:29-32
+ * write) whose rows index `queries` and whose columns index `subjects`: a
+ * handful of cells of the rectangle, without the rectangle. For p in
+ * [0, npairs) I_out[p] and D_out[p] (host arrays, either may be NULL) are bit
+ * for bit what gdist_cross_matrix(ctx, queries, subjects, ...) writes for cell
+ * (rows[p], cols[p]) with the same flags, which is what
+ * gdist_pairs(GDIST_METHOD_SORTED) gives on gdist_sets_concat(subjects, queries)
+ * for the pair (ns + rows[p], cols[p]), ns = the subjects' sets.
+ *
+ * Slot p depends on (rows[p], cols[p], flags) only: not on the order of the
+ * list, its repeats, the rest of the list or the run. No pair is "self": with
+ * the same handle passed for both collections i == j gives I = |A_i| and
+ * d = 0.0 (or the empty-set value of an empty set) by the join itself.
+ * GDIST_EMPTY_NAN is the only flag for kmer sets. There is no `method`, as in
+ * the other cross calls: the subjects' pruned dictionary cannot answer for
+ * kmers that only one query and one subject share.
+ *
+ * The list is uploaded once and sorted by query row on the device; a row's
+ * pairs are cut into work units of at most 64 pairs and, past the call's code
+ * budget (the query's size plus its listed subjects' sizes), a range of the
+ * subjects' segment index. Where a query is cut by the subjects' splitters is
+ * found per unit and cached nowhere; a unit's integer counts are added, which
+ * is exact. The outputs come back in one download.
+ *
+ * The subjects are read only, under the rule above: the one thing the call may
+ * add is their segment index. Nothing is kept on the queries.
+ * gdist_ctx_pairs_info reports this call (groups = the distinct rows of the
+ * list, units = the work units launched, as for gdist_pairs; kernel ms under
+ * option "time_kernels"); gdist_ctx_cross_info is left as it was.
+ *
+ * Two GDIST_SKETCH collections are answered by the code behind
+ * gdist_sketch_pairs(ctx, queries, subjects, ...), bit for bit, and flags may
+ * then hold GDIST_SKETCH_JACCARD beside GDIST_EMPTY_NAN.
+ *
+ * npairs == 0: GDIST_OK, nothing is touched. EINVAL, decided before any work
+ * with every output untouched: what gdist_cross_matrix refuses of the handles
+ * (null, another context or different contexts, one GDIST_SKETCH collection
+ * with one of kmer sets, kmer specs gdist_sets_concat would refuse, a
+ * collection without codes), npairs < 0 or >= 2^31, null rows or cols or both
+ * outputs null with npairs > 0, any flag but the ones above, a rows[p] outside
+ * [0, nsets of queries), a cols[p] outside [0, nsets of subjects). */
+int  gdist_cross_pairs(gdist_ctx* ctx, const gdist_sets* queries, const gdist_sets* subjects,
+                       int64_t npairs, const int64_t* rows /* into queries */,
+                       const int64_t* cols /* into subjects */, unsigned flags,
+                       int32_t* I_out, double* D_out);
 
 /* gdist_cross_within, gdist_cross_group_stats, gdist_cross_histogram: the
  * three table-free queries of one collection (gdist_within,
