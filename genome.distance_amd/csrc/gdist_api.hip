@@ -816,6 +816,16 @@ int gdist_sets_sparse_info(const gdist_sets* s, int64_t* sparse_words, int64_t* 
     });
 }
 
+int gdist_sets_sparse_triples(const gdist_sets* s, int64_t* out) {
+    return guard([&] {
+        check_sets(s);
+        GD_REQUIRE(out, "null output");
+        const bool have = s->sparse && s->sp_tri.p;
+        out[0] = have ? s->sp_triples : 0;
+        for (int k = 0; k < 4; k++) out[1 + k] = have ? s->sp_tri_lists[k] : 0;
+    });
+}
+
 int gdist_sets_variant_info(const gdist_sets* s, int64_t* kmers, int64_t* words, int64_t* entries, double* products) {
     return guard([&] {
         check_sets(s);

@@ -242,7 +242,7 @@ struct Timing {
     X(SPARSE_WTAIL, "sparse_wtail")           /* 1 (default): a walk window's leftover groups two to a step; 0: one at a time */ \
     X(SPARSE_DIAG22, "sparse_diag22")         /* 1 (default): diagonal tiles in 2 x 2 micro-tiles too (sparse_mt 2) */ \
     X(SPARSE_RPART22, "sparse_rpart22")       /* 1 (default): row-trimmed sparse tiles in 2 x 2 micro-tiles too */ \
-    X(SPARSE_MT, "sparse_mt")                 /* off-diagonal micro-tiles: 1 (1 x 2) / 2 (2 x 2, default) */   \
+    X(SPARSE_MT, "sparse_mt")                 /* off-diagonal micro-tiles: 1 (1 x 2) / 2 (2 x 2) / 3 (default: 3 x 3 over triple records; diagonal, row-trimmed tiles as 2) */ \
     X(SKETCH_K, "sketch_k")                   /* sketch merge window (1 / 2 / 4 / 6, default 2) */             \
     X(SKETCH_TILE, "sketch_tile")             /* 16: force the 16x16 sketch tile */                            \
     X(SKETCH_V2, "sketch_v2")                 /* 0: the round-2 lane map and checked merge loop */             \
@@ -480,6 +480,10 @@ struct gdist_sets {
     int64_t Ws = 0;                       // sparse words
     gdist::DevBuf sp_off;                 // int64 [ceil(nsets/128) * Ws + 1]: (set block, sparse word) -> entries
     gdist::DevBuf sp_ent;                 // 16-byte records {row code, word, column code} [sp_entries + 4]
+    gdist::DevBuf sp_toff;                // uint32 [ceil(nsets/128) * Ws + 1]: (set block, sparse word) -> triples
+    gdist::DevBuf sp_tri;                 // 32-byte triple records (sparse_triple.hpp) [sp_triples + sentinel run];
+    int64_t sp_triples = 0;               // null past 2^27 triples (the 3 x 3 walk is then left out)
+    int64_t sp_tri_lists[4] = {0, 0, 0, 0};   // (block, word) lists: empty, n mod 3 = 1, 2, 0 (n > 0)
     gdist::DevBuf sp_nc;                  // int32 [nsets]: complement bits over the sparse words
     int64_t sp_entries = 0, sp_U = 0;     // entries; valid bits of the sparse words
     int64_t sp_pos_words = 0;             // sparse words counted from their set bits (positive-sparse)

@@ -31,6 +31,7 @@
 
 #include "gdist_internal.hpp"
 #include "sparse_bounds.hpp"
+#include "sparse_triple.hpp"
 
 namespace gdist {
 namespace {
@@ -405,30 +406,10 @@ struct GroupPart {
     }
 };
 
-// LDS counter of local pair (row a, column b), as a 16-bit slot t (dword
-// t >> 1, half t & 1): row a owns dwords [64 a, 64 a + 64); column b sits in
-// dword (b >> 1) ^ (a & 63) of it, half b & 1. The XOR rotation by the row
-// spreads the products of one word (its rows x its columns) over the banks.
-// The records carry the two halves of the address precomputed (entry_codes):
-// a row entry's byte base with its rotation key, a column entry's byte offset
-// and half shift, so a product's counter costs one XOR and one shift.
-__host__ __device__ __forceinline__ int cnt_index(int a, int b) {
-    return ((a * 64 + ((b >> 1) ^ (a & 63))) << 1) | (b & 1);
-}
-__host__ __device__ __forceinline__ void cnt_pair(int t, int& a, int& b) {
-    const int d = t >> 1;
-    a = d >> 6;
-    b = (((d & 63) ^ (a & 63)) << 1) | (t & 1);
-}
-// record codes of set s (0..127): row role = byte address of its row with the
-// rotation key in bits 2-7 (row bytes 256 s, keys < 256); column role = shift
-// (s & 1) << 4 in bits 0-4 and its dword's byte offset (s >> 1) << 2 in bits 16+
-__host__ __device__ __forceinline__ uint32_t row_code(int s) { return ((uint32_t)s << 8) | ((uint32_t)(s & 63) << 2); }
-__host__ __device__ __forceinline__ uint32_t col_code(int s) {
-    return ((uint32_t)(s & 1) << 4) | (((uint32_t)(s >> 1) << 2) << 16);
-}
+// the counters' layout (cnt_index) and the records' codes: sparse_triple.hpp
 constexpr uint32_t kLastOfList = 32;     // column code bit 5 (above the shift, below the offset): the entry ends its (block, word) list
 constexpr int kSentinelRecs = 512;       // zero records after the entries (the virtual word's)
+constexpr int kSparseMtDefault = 3;      // option sparse_mt
 // the counter add of a product of row code r and column code c (byte address r ^ c >> 16)
 __device__ __forceinline__ void cnt_add(uint32_t* cnt, uint32_t r, uint32_t c, uint32_t v) {
     atomicAdd(reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(cnt) + (r ^ (c >> 16))), v << (c & 31));
@@ -462,6 +443,45 @@ __global__ void sparse_last_kernel(const int64_t* __restrict__ off, int64_t nlis
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nlists; t += stride) {
         const int64_t b = off[t], e = off[t + 1];
         if (e > b) ent[e - 1].y |= (unsigned long long)kLastOfList << 32;
+    }
+}
+
+// Triple records (sparse_triple.hpp; the 3 x 3 walk, option sparse_mt 3):
+// every (block, word) list of n entries as ceil(n / 3) records of 32 bytes.
+// The lists' triple counts (scanned into the triple offsets) and their
+// classes cls = {empty, n mod 3 = 1, 2, 0 with n > 0} (gdist_sets_sparse_triples)
+__global__ void sparse_triple_count_kernel(const int64_t* __restrict__ off, int64_t nlists,
+                                           int32_t* __restrict__ tcnt, unsigned long long* __restrict__ cls) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;     // one thread a list, the scan's last element too
+    int c = -1;
+    if (t < nlists) {
+        const int n = (int)(off[t + 1] - off[t]);
+        tcnt[t] = (n + 2) / 3;
+        c = n == 0 ? 0 : n % 3 == 0 ? 3 : n % 3;
+    } else if (t == nlists) {
+        tcnt[t] = 0;
+    }
+    for (int k = 0; k < 4; k++) {
+        const unsigned long long m = __ballot(c == k);
+        if (m && (threadIdx.x & 63) == 0) atomicAdd(&cls[k], (unsigned long long)__popcll(m));
+    }
+}
+// one thread a list: its triples, and its offset as a dword
+__global__ void sparse_triples_kernel(const int64_t* __restrict__ off, const int64_t* __restrict__ toff64,
+                                      int64_t nlists, const unsigned long long* __restrict__ word,
+                                      const uint8_t* __restrict__ set, uint32_t* __restrict__ toff,
+                                      uint4* __restrict__ tri) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > nlists) return;
+    const int64_t tb = toff64[t];
+    toff[t] = (uint32_t)tb;
+    if (t == nlists) return;
+    const int64_t b = off[t];
+    const int n = (int)(off[t + 1] - b);
+    for (int j = 0; 3 * j < n; j++) {
+        const Triple r = triple_pack(word + b + 3 * j, set + b + 3 * j, n - 3 * j < 3 ? n - 3 * j : 3);
+        tri[2 * (tb + j)] = make_uint4(r.d[0], r.d[1], r.d[2], r.d[3]);
+        tri[2 * (tb + j) + 1] = make_uint4(r.d[4], r.d[5], r.d[6], r.d[7]);
     }
 }
 
@@ -824,6 +844,72 @@ __device__ __forceinline__ void sparse_diag22_slots(const int4* __restrict__ rec
     }
 }
 
+// Off-diagonal 3 x 3 micro-tiles (option sparse_mt 3) over the triple
+// records (sparse_triple.hpp): ceil(nrow / 3) row triples x nct = ceil(ncol
+// / 3) column triples per word, the quotient of the 2 x 2 walk with 2 nct in
+// the reciprocal's low byte (<= 86) and both offsets in records of 32 bytes.
+// Nine products a slot from four 16-byte loads, where 2 x 2 takes four loads
+// for four: the texture address unit's cost is per lane and load, not per
+// byte. A triple's missing entries are word 0 / set 0 and their products 0:
+// no last-of-list flag. A lane adds only its products that are not zero: the
+// kernel's time follows the LDS cycles of its counter adds (SQ_LDS_IDX_ACTIVE
+// over the launch's cycles is 0.48 for both walks), and a
+// ds_add_u32 pays for every active lane's bank whatever it adds, so the
+// padding's and the disjoint entries' zeros cost bank conflicts for nothing.
+// Not for row-trimmed tiles (a triple cannot be trimmed to an entry range)
+// nor diagonal ones.
+template <int SU>
+__device__ __forceinline__ void sparse_off33_slots(const int4* __restrict__ rec,
+                                                   const unsigned long long* __restrict__ masks, int W0, int last,
+                                                   int fb, int lane, const SparseWalk& e, uint32_t* __restrict__ cnt) {
+    int4 r[SU];
+    unsigned long long m[SU];
+    const unsigned long long* mk = masks + ((fb - W0) >> 6);
+#pragma unroll
+    for (int u = 0; u < SU; u++) m[u] = mk[u];
+#pragma unroll
+    for (int u = 0; u < SU; u++) r[u] = rec[slot_rec(last, fb + 64 * u, m[u])];
+    uint32_t ri[SU], ci[SU];
+#pragma unroll
+    for (int u = 0; u < SU; u++) {
+        const int q2 = 2 * (fb + 64 * u) + 2 * lane + r[u].x;
+        const float rcp = __int_as_float(r[u].w);
+        const int xc = (int)__builtin_fmaf((float)q2, rcp, rcp);
+        const int yc2 = q2 - (int)__umul24((uint32_t)xc, (uint32_t)r[u].w & 0xFFu);
+        ri[u] = (uint32_t)r[u].y + ((uint32_t)xc << 5);
+        ci[u] = (uint32_t)r[u].z + ((uint32_t)yc2 << 4);
+    }
+    uint4 a0[SU], a1[SU], b0[SU], b1[SU];          // {w0, w1}, {w2, codes} of the row and the column triple
+#pragma unroll
+    for (int u = 0; u < SU; u++) {
+        const char* pa = e.eA + ri[u];
+        const char* pb = e.eB + ci[u];
+        a0[u] = *reinterpret_cast<const uint4*>(pa);
+        a1[u] = *reinterpret_cast<const uint4*>(pa + 16);
+        b0[u] = *reinterpret_cast<const uint4*>(pb);
+        b1[u] = *reinterpret_cast<const uint4*>(pb + 16);
+    }
+#pragma unroll
+    for (int u = 0; u < SU; u++) {
+        const uint32_t al[3] = {a0[u].x, a0[u].z, a1[u].x}, ah[3] = {a0[u].y, a0[u].w, a1[u].y};
+        const uint32_t bl[3] = {b0[u].x, b0[u].z, b1[u].x}, bh[3] = {b0[u].y, b0[u].w, b1[u].y};
+#pragma unroll
+        for (int y = 0; y < 3; y++) {
+            const uint32_t co = triple_coff(b1[u].z, b1[u].w, y), sh = triple_shift(b1[u].z, b1[u].w, y);
+#pragma unroll
+            for (int x = 0; x < 3; x++) {
+                const uint32_t v = (uint32_t)(__popc(al[x] & bl[y]) + __popc(ah[x] & bh[y]));
+                const uint32_t rc = triple_row(a1[u].z, a1[u].w, x);
+                if (v) atomicAdd(reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(cnt) + (rc ^ co)), v << sh);
+            }
+        }
+    }
+}
+
+// 3 x 3 slots per lane in flight: a slot holds 16 dwords of records, and
+// three of them take the <3, 2> kernel to 64 bytes of scratch a lane
+constexpr int kTripleSlots = 2;
+
 // one step of SU groups of 64 slots from slot fb, in the walk's mode
 template <int SU, int MODE>
 __device__ __forceinline__ void sparse_step(const int4* __restrict__ rec, const unsigned long long* __restrict__ masks,
@@ -832,6 +918,7 @@ __device__ __forceinline__ void sparse_step(const int4* __restrict__ rec, const 
     if (MODE == 0) sparse_diag_slots<SU>(rec, masks, W0, last, fb, lane, e, cnt, mirror);
     else if (MODE == 1) sparse_off_slots<SU>(rec, masks, W0, last, fb, lane, e, cnt);
     else if (MODE == 2) sparse_off22_slots<SU>(rec, masks, W0, last, fb, lane, e, cnt);
+    else if (MODE == 4) sparse_off33_slots<SU>(rec, masks, W0, last, fb, lane, e, cnt);
     else sparse_diag22_slots<SU>(rec, masks, W0, last, fb, lane, e, cnt, mirror);
 }
 
@@ -871,7 +958,7 @@ __device__ __forceinline__ void sparse_walk(const int4* __restrict__ rec, unsign
 // offsets, bases of the chunk's records, row trimming, shape flags.
 struct TileWalk {
     const uint32_t* offA;                 // the int64 offsets as dwords: entries < 2^28 in all, so an
-    const uint32_t* offB;                 // offset is its low dword, [2 s] of this view
+    const uint32_t* offB;                 // offset is its low dword, [2 s] of this view (t33: the triple offsets, [s])
     const ulonglong2* ent;
     uint32_t ra0, cb0;                    // chunk bases (entries < 2^28 in all: byte offsets)
     uint32_t zA, zB;                      // the sentinel run from those bases
@@ -880,6 +967,7 @@ struct TileWalk {
     bool rpart, diag, mirror, r22;
     bool d22;                             // diagonal tiles in 2 x 2 micro-tiles (MT 2, option sparse_diag22)
     bool wtail;                           // a window's leftover groups two to a step (option sparse_wtail)
+    bool t33;                             // the tile walks triple records in 3 x 3 micro-tiles (option sparse_mt 3)
 };
 
 // One batch of words [s0, be), be - s0 <= kBatchWords (lane l takes word
@@ -899,14 +987,16 @@ __device__ __forceinline__ void global_batch(const TileWalk& tc, int64_t s0, int
     const bool rpart = tc.rpart, diag = tc.diag, mirror = tc.mirror, r22 = tc.r22;
     const bool d22 = MT == 2 && tc.d22;
     const bool wtail = tc.wtail;
+    const bool t33 = MT == 2 && tc.t33;
+    const int osh = t33 ? 0 : 1, rsh = t33 ? 5 : 4;          // offsets' stride in dwords, a record's bytes
     // each bound is loaded once: lane l <= bn takes the starts of word s0 + l
     // (lane bn: the ends of the batch's last word), and a word's lists end
     // where the next lane's start
     const int bn = be - s0 < kBatchWords ? (int)(be - s0) : kBatchWords;
     uint32_t rb = ra0, cb = cb0;
     if (lane <= bn) {
-        rb = offA[2 * (s0 + lane)];
-        cb = offB[2 * (s0 + lane)];
+        rb = offA[(s0 + lane) << osh];
+        cb = offB[(s0 + lane) << osh];
     }
     const uint32_t re = wave_next_lane(rb), ce = wave_next_lane(cb);
     int nr = 0, ncl = 0;
@@ -924,10 +1014,11 @@ __device__ __forceinline__ void global_batch(const TileWalk& tc, int64_t s0, int
             nr = en > a ? en - a : 0;
         }
     }
-    const int ncd = diag ? ncl : (ncl + 1) >> 1;   // column pairs per row (pair) (off-diagonal micro-tiles)
+    // column pairs per row (pair) (off-diagonal micro-tiles); t33: nr and ncl count triples
+    const int ncd = diag || t33 ? ncl : (ncl + 1) >> 1;
     const int hp = (nr + 1) >> 1;                 // 2 x 2 diagonal: pairs of entries
     const int P = diag ? (d22 ? (nr >= 2 ? hp * (hp + 1) / 2 : 0) : nr * (nr - 1) / 2)
-                       : (r22 ? hp : nr) * ncd;
+                       : (r22 && !t33 ? hp : nr) * ncd;
     const int incl = wave_scan_incl(P);
     const int total = __builtin_amdgcn_readlane(incl, 63);      // uniform: the walk's loop stays scalar
     // the records of the words with slots, compacted in slot order, and the
@@ -939,20 +1030,21 @@ __device__ __forceinline__ void global_batch(const TileWalk& tc, int64_t s0, int
             wrec[k] = make_int4(-(incl - P), (int32_t)(rb - ra0), 0, 0);
         } else {
             const uint32_t rcp = (uint32_t)__float_as_int(__builtin_amdgcn_rcpf(2.0f * (float)ncd));
-            wrec[k] = make_int4(-2 * (incl - P), (int32_t)((rb - ra0) << 4), (int32_t)((cb - cb0) << 4),
+            wrec[k] = make_int4(-2 * (incl - P), (int32_t)((rb - ra0) << rsh), (int32_t)((cb - cb0) << rsh),
                                 (int32_t)((rcp & 0xFFFFFF00u) | (uint32_t)(2 * ncd)));
         }
     }
     if (lane == 0) {
         const int nw = __popcll(nz);
         wrec[nw] = diag ? make_int4(-total, (int32_t)zA, 0, 0)
-                        : make_int4(-2 * total, (int32_t)(zA << 4), (int32_t)(zB << 4), 0);
+                        : make_int4(-2 * total, (int32_t)(zA << rsh), (int32_t)(zB << rsh), 0);
     }
     const int last = P > 0 ? incl - 1 : 0x7FFFFFFF;
     __builtin_amdgcn_wave_barrier();
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
     if (MT == 2 && diag && d22) sparse_walk<2, 3>(wrec, masks, last, total, lane, e, cnt, mirror, wtail);
     else if (diag) sparse_walk<SUN, 0>(wrec, masks, last, total, lane, e, cnt, mirror, wtail);
+    else if (MT == 2 && t33) sparse_walk<kTripleSlots, MT == 2 ? 4 : 1>(wrec, masks, last, total, lane, e, cnt, false, wtail);
     else if (MT == 2 && r22) sparse_walk<MT == 2 ? SUN : 1, 2>(wrec, masks, last, total, lane, e, cnt, false, wtail);
     else sparse_walk<SUN, 1>(wrec, masks, last, total, lane, e, cnt, false, wtail);
 }
@@ -964,7 +1056,9 @@ __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
     const int2* __restrict__ wgmap, int nchunks, int64_t r0, int64_t r1,
     int64_t c0, int64_t c1, int upper, int32_t* __restrict__ I, int64_t ldI, int32_t* __restrict__ part, int64_t Wdp,
     int64_t N, const unsigned long long* __restrict__ slab_bits, int slabs, GroupPart gp, int xmap, int ntiles,
-    RareSlab rs, int dyn, int diag22, int rpart22, int batch, int wtail) {
+    RareSlab rs, int dyn, int diag22, int rpart22, int batch, int wtail, const uint32_t* __restrict__ toff,
+    const uint4* __restrict__ tri) {
+    // toff / tri: the triple offsets and records (MT 2 with option sparse_mt 3; null: every tile in 2 x 2)
     // gp: the group tier's part of every pair, added with the constant part
     // slab_bits / slabs: the in-kernel fold's dense words (set-major [N][Wdp])
     __shared__ __attribute__((aligned(16))) uint32_t cnt[SB * SB / 2];   // 32 KiB, 16-bit counters (cnt_index layout)
@@ -1029,15 +1123,21 @@ __global__ __launch_bounds__(SNT, 8) void sparse_tile_kernel(
     __syncthreads();
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int64_t sb = cbnd[ch], se = cbnd[ch + 1];          // the chunk's sparse words
-    const int64_t* offA = off + A * Ws;
-    const int64_t* offB = off + B * Ws;
-    const int64_t ra0 = offA[sb], cb0 = offB[sb];           // chunk bases (entries < 2^28 in all: byte offsets)
-    const int64_t ntot = off[(int64_t)ceil_div(N, SB) * Ws];         // entries of every block: the sentinel run
-    const uint32_t zA = (uint32_t)(ntot - ra0), zB = (uint32_t)(ntot - cb0);
-    const TileWalk tc{reinterpret_cast<const uint32_t*>(offA), reinterpret_cast<const uint32_t*>(offB), ent,
-                      (uint32_t)ra0, (uint32_t)cb0, zA, zB,
-                      SparseWalk{reinterpret_cast<const char*>(ent + ra0), reinterpret_cast<const char*>(ent + cb0)},
-                      rlo, rhi, rpart, diag, mirror, r22, diag22 != 0, wtail != 0};
+    // 3 x 3 micro-tiles over the triple records: off-diagonal tiles whose rows are not trimmed
+    const bool t33 = MT == 2 && toff && !diag && !rpart;
+    const uint32_t* offA = t33 ? toff + A * Ws : reinterpret_cast<const uint32_t*>(off + A * Ws);
+    const uint32_t* offB = t33 ? toff + B * Ws : reinterpret_cast<const uint32_t*>(off + B * Ws);
+    const int osh = t33 ? 0 : 1, rsh = t33 ? 5 : 4;
+    // chunk bases (entries < 2^28, triples < 2^27 in all: byte offsets)
+    const uint32_t ra0 = offA[sb << osh], cb0 = offB[sb << osh];
+    // entries (triples) of every block: the sentinel run
+    const int64_t nlists = (int64_t)ceil_div(N, SB) * Ws;
+    const uint32_t ntot = t33 ? toff[nlists] : (uint32_t)off[nlists];
+    const uint32_t zA = ntot - ra0, zB = ntot - cb0;
+    const char* recs = t33 ? reinterpret_cast<const char*>(tri) : reinterpret_cast<const char*>(ent);
+    const TileWalk tc{offA, offB, ent, ra0, cb0, zA, zB,
+                      SparseWalk{recs + ((int64_t)ra0 << rsh), recs + ((int64_t)cb0 << rsh)},
+                      rlo, rhi, rpart, diag, mirror, r22, diag22 != 0, wtail != 0, t33};
     int4* wrec = &rec[wv][0];
     unsigned long long* masks = reinterpret_cast<unsigned long long*>(&rec[wv][kBatchWords + 1]);
     // The batch size bw, one for the whole chunk (option sparse_batch 1..48
@@ -1260,6 +1360,10 @@ void free_sparse(gdist_sets* s) {
     s->dbits.release();
     s->sp_off.release();
     s->sp_ent.release();
+    s->sp_toff.release();
+    s->sp_tri.release();
+    s->sp_triples = 0;
+    for (int64_t& c : s->sp_tri_lists) c = 0;
     s->sp_nc.release();
     s->sparse = false;
     s->Wd = s->Ws = s->sp_entries = s->sp_U = 0;
@@ -1555,6 +1659,35 @@ void build_sparse_words(gdist_ctx* ctx, gdist_sets* s) {
                                                                 s->sp_ent.as<ulonglong2>());
     }
     GD_HIP(hipGetLastError());
+    {   // the same entries as triple records with a 32-bit offset table of
+        // their own (the 3 x 3 walk); the walk addresses them by 32-bit byte
+        // offsets, so past 2^27 triples they are left out (the 2 x 2 walk stays)
+        const int64_t nl = nblk * Ws;
+        DevBuf tcnt((nl + 1) * 4, st), t64((nl + 1) * 8, st), cls(4 * 8, st);
+        GD_HIP(hipMemsetAsync(cls.p, 0, 4 * 8, st));
+        sparse_triple_count_kernel<<<(unsigned)ceil_div(nl + 1, 256), 256, 0, st>>>(
+            s->sp_off.as<int64_t>(), nl, tcnt.as<int32_t>(), cls.as<unsigned long long>());
+        GD_HIP(hipGetLastError());
+        exclusive_scan_i32_to_i64(ctx, tcnt.as<int32_t>(), t64.as<int64_t>(), (size_t)(nl + 1));
+        int64_t ntri = 0;
+        unsigned long long hc[4] = {0, 0, 0, 0};
+        d2h(&ntri, t64.as<int64_t>() + nl, 8, st);
+        d2h(hc, cls.p, 4 * 8, st);
+        if (ntri + kSentinelTriples < (int64_t(1) << 27)) {
+            s->sp_toff.alloc((nl + 1) * 4, st);
+            s->sp_tri.alloc((ntri + kSentinelTriples) * kTripleBytes, st);
+            GD_HIP(hipMemsetAsync(s->sp_tri.as<char>() + ntri * kTripleBytes, 0, kSentinelTriples * kTripleBytes, st));
+            sparse_triples_kernel<<<(unsigned)ceil_div(nl + 1, 256), 256, 0, st>>>(
+                s->sp_off.as<int64_t>(), t64.as<int64_t>(), nl, sp_word.as<unsigned long long>(),
+                sp_set.as<uint8_t>(), s->sp_toff.as<uint32_t>(), s->sp_tri.as<uint4>());
+            GD_HIP(hipGetLastError());
+            s->sp_triples = ntri;
+            for (int k = 0; k < 4; k++) s->sp_tri_lists[k] = (int64_t)hc[k];
+        } else if (ctx->trace()) {
+            fprintf(stderr, "gdist: %lld sparse triples exceed the 3 x 3 walk's 2^27: the 2 x 2 walk stays\n",
+                    (long long)ntri);
+        }
+    }
     if (grouped) {
         // the group part of every pair: T from the pattern rows, V came with
         // the entries (sparse_fill_kernel); the set -> group map stays
@@ -1972,10 +2105,13 @@ bool sparse_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
     // LDS-limited; profiles/r01/sparse/occ_{3,8}.json)
     // 2 x 2 micro-tiles, 3 slots (12 products) per lane in flight; 1 x 2 with
     // 4 (C2 A/B, profiles/r04/s21/ab, r04/s13/ab_sun: 2 x 2 with 4 spills)
-    const int mt = (int)ctx->option(OPT_SPARSE_MT, 2);
-    const int sun = (int)ctx->option(OPT_SPARSE_SUN, mt == 2 ? 3 : 4);
+    int mt = (int)ctx->option(OPT_SPARSE_MT, kSparseMtDefault);
+    const int sun = (int)ctx->option(OPT_SPARSE_SUN, mt >= 2 ? 3 : 4);
     GD_REQUIRE(sun >= 2 && sun <= 4, "sparse_sun: 2, 3 or 4");
-    GD_REQUIRE(mt == 1 || mt == 2, "sparse_mt: 1 (1 x 2 micro-tiles) or 2 (2 x 2)");
+    GD_REQUIRE(mt >= 1 && mt <= 3, "sparse_mt: 1 (1 x 2 micro-tiles), 2 (2 x 2) or 3 (3 x 3 over triples)");
+    // 3 x 3: the 2 x 2 kernel with the triple records (a collection without them keeps 2 x 2)
+    const bool t33 = mt == 3 && s->sp_tri.p;
+    if (mt == 3) mt = 2;
     const int batch = (int)ctx->option(OPT_SPARSE_BATCH, 0);
     GD_REQUIRE(batch >= 0 && batch <= kBatchWords, "sparse_batch: 0 (by the chunk) or 1..48 words");
     auto kern = mt == 2 ? (sun == 2 ? sparse_tile_kernel<2, 2> : sun == 4 ? sparse_tile_kernel<4, 2> : sparse_tile_kernel<3, 2>)
@@ -2006,7 +2142,9 @@ bool sparse_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
                                          group_part(s), xmap ? 1 : 0, (int)nt, rs,
                                          (int)ctx->option(OPT_SPARSE_DYN, 1), (int)ctx->option(OPT_SPARSE_DIAG22, 1),
                                          (int)ctx->option(OPT_SPARSE_RPART22, 1), batch,
-                                         (int)ctx->option(OPT_SPARSE_WTAIL, 1));
+                                         (int)ctx->option(OPT_SPARSE_WTAIL, 1),
+                                         t33 ? s->sp_toff.as<uint32_t>() : nullptr,
+                                         t33 ? s->sp_tri.as<uint4>() : nullptr);
     GD_HIP(hipGetLastError());
     ft.end();
     if (pp) {

@@ -61,7 +61,7 @@ def tree_source_hash() -> str:
     order (csrc/*.hip by name, csrc/gdist_internal.hpp, csrc/sparse_bounds.hpp,
     csrc/group_stats_host.hpp, csrc/cross_plan.hpp, csrc/sketch_cross_merge.hpp,
     csrc/sketch_wave_merge.hpp, csrc/pair_list.hpp, csrc/cross_cut.hpp,
-    include/gdist.h)."""
+    csrc/sparse_triple.hpp, include/gdist.h)."""
     import glob
     import hashlib
     files = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hip")))
@@ -69,6 +69,7 @@ def tree_source_hash() -> str:
               os.path.join(_PKG, "csrc", "group_stats_host.hpp"), os.path.join(_PKG, "csrc", "cross_plan.hpp"),
               os.path.join(_PKG, "csrc", "sketch_cross_merge.hpp"), os.path.join(_PKG, "csrc", "sketch_wave_merge.hpp"),
               os.path.join(_PKG, "csrc", "pair_list.hpp"), os.path.join(_PKG, "csrc", "cross_cut.hpp"),
+              os.path.join(_PKG, "csrc", "sparse_triple.hpp"),
               os.path.join(_REPO, "include", "gdist.h")]
     h = hashlib.sha256()
     for f in files:
@@ -135,6 +136,7 @@ _SIGS = {
     "gdist_sets_variant_layout": (C.c_int, [_setp, C.POINTER(C.c_int), C.POINTER(C.c_int), _i64p]),
     "gdist_sets_group_info": (C.c_int, [_setp, _i64p, _i64p]),
     "gdist_sets_sparse_sides": (C.c_int, [_setp, _i64p, _i64p]),
+    "gdist_sets_sparse_triples": (C.c_int, [_setp, _i64p]),
     "gdist_sets_sparse_pairs": (C.c_int, [_setp, C.POINTER(C.c_double)]),
     "gdist_sets_bitset_info": (C.c_int, [_setp, _i64p, _i64p]),
     "gdist_sets_bitset_download": (C.c_int, [_setp, _u64p]),

@@ -961,6 +961,13 @@ class KmerSets(_Handle):
         L.check(L.lib.gdist_sets_sparse_sides(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def sparse_triples(self) -> tuple[int, int, int, int, int]:
+        """(triple records, empty lists, lists with n mod 3 = 1, 2, 0 and n > 0) of the
+        sparse words' (set block, word) lists (gdist_sets_sparse_triples)."""
+        out = (C.c_int64 * 5)()
+        L.check(L.lib.gdist_sets_sparse_triples(self.h, out))
+        return tuple(int(v) for v in out)
+
     def sparse_pairs(self) -> float:
         """The sparse tile kernel's products: sum over sparse words of z (z - 1) / 2."""
         p = C.c_double()

@@ -312,6 +312,13 @@ int  gdist_sets_sparse_sides(const gdist_sets* sets, int64_t* complement_words, 
  * word's entries once (0 without the split). Diagnostics: the bench line's
  * VALU per 64 products. */
 int  gdist_sets_sparse_pairs(const gdist_sets* sets, double* pairs);
+/* The triple records of the sparse words (the 3 x 3 walk of
+ * option "sparse_mt" 3): every (set block, sparse word) list of n entries as
+ * ceil(n / 3) records. out[0] = the records, out[1..4] = the lists that are
+ * empty and those with n mod 3 = 1, 2 and 0 (n > 0), counted at build time.
+ * Zeros without the split, or where the records were left out (more than
+ * 2^27 of them). Diagnostics and tests. */
+int  gdist_sets_sparse_triples(const gdist_sets* sets, int64_t* out);
 /* The group tier of the sparse words: groups of sets (e.g.
  * the clades of a structured collection) whose members all carry the same
  * pattern in a word; those words keep per member only the residual entries
