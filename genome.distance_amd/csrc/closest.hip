@@ -58,7 +58,7 @@ __device__ __forceinline__ void wave_sort(unsigned long long* kd, uint32_t* kc, 
 
 // Rows [q0, q0 + nrows) against the chunk's columns [c0, c0 + nc).
 //  FromCounts: src is I (int32, row a / column b at src[a * ld + b]) and d is
-//  the Java expression of epilogue_kernel (bitset.hip), fp64, no contraction,
+//  the Java expression of epilogue_kernel (matrix_step.hip), fp64, no contraction,
 //  with the row's size from roff and the column's from coff (one collection:
 //  the same array; gdist_cross_closest: the queries' and the subjects');
 //  else src is D (double, the same layout).

@@ -152,7 +152,7 @@ static void use_device(gdist_ctx* ctx) {
     GD_REQUIRE(ctx != nullptr, "null context");
     GD_HIP(hipSetDevice(ctx->device));
     // every API entry counts: a pipelined step is in an unbroken run only
-    // when the entry before it was one too (bitset.hip bitset_matrix_fused)
+    // when the entry before it was one too (matrix_step.hip bitset_matrix_fused)
     ctx->api_seq++;
 }
 
@@ -1209,7 +1209,7 @@ int gdist_intersect_matrix(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, i
             if (dev) { dD = D_out; ldD = ld; }
             else { tD.alloc((size_t)nr * nc * 8, st); dD = tD.as<double>(); ldD = nc; }
         }
-        // the fused sparse step writes I and D itself (bitset.hip)
+        // the fused sparse step writes I and D itself (matrix_step.hip)
         const bool fused = m == GDIST_METHOD_BITSET && dD &&
                            bitset_matrix_fused(ctx, s, r0, r1, c0, c1, upper, flags, dI, ldI, dD, ldD);
         if (!fused) {

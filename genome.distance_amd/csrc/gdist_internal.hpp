@@ -331,7 +331,7 @@ struct Trace {
 };
 
 // Dictionary summary: sorted distinct codes + the number of sets holding each
-// (bitset.hip; pack.hip keeps one per pack chunk, gdist_sets::pack_sum)
+// (bitset_build.hip; pack.hip keeps one per pack chunk, gdist_sets::pack_sum)
 struct Summary {
     DevBuf codes;    // uint64 [n]
     DevBuf counts;   // uint32 [n]
@@ -556,12 +556,16 @@ void exclusive_scan_i64(gdist_ctx* ctx, const int64_t* in, int64_t* out, size_t 
 void exclusive_scan_i32_to_i64(gdist_ctx* ctx, const int32_t* in, int64_t* out, size_t n);
 int code_bits(int kind, int k, unsigned flags);
 
-// bitset.hip — dictionary summaries (struct Summary above gdist_sets)
+// bitset_build.hip — dictionary summaries (struct Summary above gdist_sets)
 struct SummaryView {
     const uint64_t* codes;
     const uint32_t* counts;
     int64_t n;
 };
+constexpr int64_t kBitsChunk = int64_t(1) << 30;   // codes per working chunk of the summary and the sorting fill
+// (keys sorted) -> runs: unique codes, run starts, run count
+void runs_of(gdist_ctx* ctx, const uint64_t* keys, int64_t n, DevBuf& flag, DevBuf& pos, DevBuf& uniq, DevBuf& start,
+             int64_t& nruns);
 void local_summary(gdist_ctx* ctx, const gdist_sets* s, Summary& out);
 // T (in/out): rare-tier threshold; T < 0 picks the cost-optimal one for a
 // collection of nsets sets from the histogram of kmer counts
@@ -575,6 +579,7 @@ int64_t auto_rare_threshold(int64_t nsets);
 // cost-optimal rare threshold from hist[c] = number of kmers held by c sets
 // (c = 0..nsets); the chosen T is reported by gdist_sets_rare_info
 int64_t choose_rare_threshold(const std::vector<uint64_t>& hist, int64_t nsets);
+// bitset_fill.hip — the rows of bits and the rare records from the dictionary
 // perm (optional): bit position of each dense rank (locus order)
 // hook (optional, default fill only): called per chunk of sets [s0, s1)
 // with the chunk's position array (u32 per code from code `base`; ~0 outside
@@ -593,6 +598,7 @@ void fill_bits(gdist_ctx* ctx, const gdist_sets* s, const uint64_t* dict, int64_
                unsigned long long* bits, const uint64_t* rare, int64_t Ur, int64_t id_base,
                unsigned long long* rare_out, int64_t rare_cap, int64_t* rare_written,
                const uint32_t* perm = nullptr, const FillHook& hook = FillHook(), int64_t sa = 0, int64_t sb = -1);
+// bitset_build.hip: rare records (rank << 32 | set) -> the posting lists and the set -> list CSR on `s`
 void build_postings(gdist_ctx* ctx, gdist_sets* s, unsigned long long* recs, int64_t n, int64_t Ur);
 // Cost model (seconds), calibrated on MI355X from per-kernel rocprofv3
 // averages (scripts/calib_rare.sh; profiles/r01/rare_model): bitset = dense
@@ -630,7 +636,7 @@ inline RareChoice rare_choice(const RareTier& t, double f_area, double f_rows) {
     c.row_major = c.row_s < c.list_s * kRareOverlapExposed;
     return c;
 }
-RareTier rare_tier(const gdist_sets* s);
+RareTier rare_tier(const gdist_sets* s);   // rare.hip
 // pairs of the block rows [r0, r1) x cols [c0, c1) (upper: only j > i)
 double block_pairs(int64_t r0, int64_t r1, int64_t c0, int64_t c1, bool upper);
 // modelled seconds of bitset_matrix on the block (dense + the rare kernel it picks)
@@ -651,6 +657,37 @@ void bitset_matrix(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, 
 bool bitset_matrix_fused(gdist_ctx* ctx, const gdist_sets* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1,
                          bool upper, unsigned flags, int32_t* d_I, int64_t ldI, double* d_D, int64_t ldD,
                          bool pipelined = false);
+// What bitset_matrix (matrix_step.hip) orders: one launcher per kernel family
+// of a step. Each enqueues on the stream it is given and synchronises nothing.
+// rows [r0, r1) x columns [c0, c1) of the N x N table (upper: only pairs j > i)
+struct Region {
+    int64_t r0, r1, c0, c1;
+    bool upper;
+};
+// rare.hip: list-major walk, every list's pairs in the region added to I with atomics
+void rare_pairs_launch(gdist_ctx* ctx, const gdist_sets* s, const Region& g, int32_t* d_I, int64_t ldI, hipStream_t rs);
+// rare.hip: row-major walk (LDS column chunks, or every record once: option
+// rare_direct); atomic_flush: the rows are added with atomics (other writers of I run beside it)
+void rare_rows_launch(gdist_ctx* ctx, const gdist_sets* s, const Region& g, int32_t* d_I, int64_t ldI, hipStream_t rs,
+                      bool atomic_flush);
+// rare.hip, the row query: cnt[t] += rare kmers set q shares with set t, on the context's stream
+void rare_query_launch(gdist_ctx* ctx, const gdist_sets* s, int64_t q, int32_t* cnt);
+// rare.hip: I[c] += cnt[cols[c]] for the ncols requested columns
+void gather_add_launch(gdist_ctx* ctx, const int64_t* d_cols, int64_t ncols, const int32_t* cnt, int32_t* d_I);
+// bitset.hip: which MFMA dense-tile kernel a step of plan p runs (options
+// bitset_mfma_raw / _km / _store / _sched / _plane). The ordering reads `store`:
+// tiles that store their counts must finish before any other family adds.
+struct MfmaChoice {
+    bool raw, km2, store, spread, plane;
+    int km;   // words a stage
+};
+MfmaChoice mfma_choice(gdist_ctx* ctx, const gdist_sets* s, const MatrixPlan& p);
+// bitset.hip: the region's dense tiles (MFMA when the plan has MFMA tiles, else
+// AND+popcount with their diagonal and partial-row launches) on the context's
+// stream, K split for the chip; side: other families run beside them. Launches
+// nothing when there are no dense words or the sparse flush counts them.
+void dense_tiles_launch(gdist_ctx* ctx, const gdist_sets* s, const MatrixPlan& p, const MfmaChoice& m, const Region& g,
+                        bool side, int32_t* d_I, int64_t ldI);
 
 // sparse.hip — locus order of the dense dictionary, complement-sparse words
 constexpr int kGuides = 8;                       // guide sequences per packed collection (C2-realistic, 8
@@ -770,14 +807,16 @@ void sorted_row(gdist_ctx* ctx, const gdist_sets* s, int64_t q, const int64_t* d
 void segment_rows(gdist_ctx* ctx, const uint64_t* d_codes, const int64_t* d_off, int64_t nsets,
                   const uint64_t* d_split, int nseg, int64_t* d_out);
 
+// bitset.hip: one query row q against the columns d_cols, every tier's count (synchronises the stream)
 void bitset_row(gdist_ctx* ctx, const gdist_sets* s, int64_t q, const int64_t* d_cols, int64_t ncols,
                 int32_t* d_I);
-void row_epilogue(gdist_ctx* ctx, const gdist_sets* s, int64_t q, const int64_t* d_cols, int64_t ncols,
-                  unsigned flags, const int32_t* d_I, double* d_D);
-
-// epilogue (bitset.hip): D from I and set sizes, Java expression, fp64
+// reps.hip
 void greedy_reps(gdist_ctx* ctx, gdist_sets* s, int method, double t, const int64_t* tie_rank, int32_t* is_rep,
                  int64_t* rep_of, double* rep_dist, int64_t* nreps);
+
+// epilogue (matrix_step.hip): D from I and set sizes, Java expression, fp64
+void row_epilogue(gdist_ctx* ctx, const gdist_sets* s, int64_t q, const int64_t* d_cols, int64_t ncols,
+                  unsigned flags, const int32_t* d_I, double* d_D);
 // zero I over the region, only entries with j > i when upper (the others
 // belong to the caller: gdist.h, GDIST_UPPER_TRIANGLE)
 void zero_counts(gdist_ctx* ctx, int64_t r0, int64_t r1, int64_t c0, int64_t c1, bool upper, int32_t* d_I,
@@ -1056,6 +1095,11 @@ void sketch_matrix(gdist_ctx* ctx, const gdist_sets* sk, int64_t r0, int64_t r1,
                    int64_t c1, unsigned flags, int32_t* d_common, double* d_D, int64_t ld);
 
 __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// blocks of a grid-stride launch over n elements, at least 1 and at most cap
+inline int grid_for(int64_t n, int block = 256, int64_t cap = 256 * 32) {
+    int64_t g = ceil_div(n, block);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
+}
 
 // HIP events around one kernel family's launches on stream st (option
 // time_kernels, calls not captured): gdist_ctx_kernel_ms reads them

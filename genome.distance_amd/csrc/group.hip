@@ -69,7 +69,7 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
 // blockIdx.y. A work item is (row, segment of kSegCols columns); wave w of
 // the launch takes the items w, w + waves, ...
 //  FromCounts: src is I (int32, row a / column b at src[a * ld + b]) and d is
-//  the Java expression of epilogue_kernel (bitset.hip) and
+//  the Java expression of epilogue_kernel (matrix_step.hip) and
 //  closest_select_kernel, fp64, no contraction; else src is D (double).
 //  The row's size and label come from roff / rlabels ([.][nrsets]), the
 //  column's from coff / clabels ([.][ncsets]): one collection passes the same

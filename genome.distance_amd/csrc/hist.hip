@@ -51,7 +51,7 @@ constexpr int kMaxSlots = 2 * kMaxBuckets + 3;
 //  column's from coff / clabels ([.][ncsets]): one collection passes the same
 //  pointers twice, the cross calls (cross.hip) the queries' and the subjects'.
 //  FromCounts: src is I (int32, row a / column b at src[a * ld + b]) and d is
-//  the Java expression of epilogue_kernel (bitset.hip), closest_select_kernel
+//  the Java expression of epilogue_kernel (matrix_step.hip), closest_select_kernel
 //  and group_reduce_kernel, fp64, no contraction; else src is D (double).
 template <bool FromCounts>
 __global__ __launch_bounds__(256) void hist_kernel(

@@ -36,11 +36,6 @@ __host__ __device__ inline uint64_t mix64(uint64_t z) {
     return z ^ (z >> 31);
 }
 
-inline int grid_for(int64_t n, int block = 256, int64_t cap = 256 * 32) {
-    int64_t g = ceil_div(n, block);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
-
 // bucket[set * S + t] = (min over the signature of mix(x ^ salt_t)) mod B
 __global__ __launch_bounds__(256) void lsh_keys_kernel(const int32_t* __restrict__ sig, const int64_t* __restrict__ off,
                                                        int64_t nsets, int S, int B, const uint64_t* __restrict__ salts,

@@ -370,11 +370,6 @@ __global__ void cm_set_offsets_kernel(const uint64_t* __restrict__ u, int64_t n,
     off[s] = base + lo;
 }
 
-inline int grid_for(int64_t n, int block = 256, int64_t cap = 256 * 32) {
-    int64_t g = ceil_div(n, block);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
-
 __global__ void valid_flags_kernel(const int32_t* __restrict__ ids, int64_t n, int32_t invalid,
                                    int32_t* __restrict__ flag) {
     int64_t stride = (int64_t)gridDim.x * blockDim.x;

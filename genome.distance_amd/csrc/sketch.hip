@@ -25,11 +25,6 @@
 namespace gdist {
 namespace {
 
-inline int grid_for(int64_t n, int block = 256, int64_t cap = 256 * 32) {
-    int64_t g = ceil_div(n, block);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
-
 __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 
 // kmer string byte t of code (first char most significant), decoded per spec

@@ -36,11 +36,6 @@
 namespace gdist {
 namespace {
 
-inline int grid_for(int64_t n, int block = 256, int64_t cap = 256 * 32) {
-    int64_t g = ceil_div(n, block);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
-
 constexpr int SB = 128;                  // sets per block of the sparse entry index (tile edge)
 constexpr int SNT = 512;                 // threads per workgroup (4 per CU, LDS-limited: 8 waves per SIMD)
 constexpr int kBucketShift = 10;         // sparse words per complement-bit bucket: 1024
@@ -485,7 +480,7 @@ __global__ void sparse_triples_kernel(const int64_t* __restrict__ off, const int
     }
 }
 
-// the rare tier's set -> list CSR (bitset.hip build_postings), walked in every step
+// the rare tier's set -> list CSR (bitset_build.hip build_postings), walked in every step
 struct RareRows {
     const int64_t* soff = nullptr;        // [N + 1] (null: no walk)
     const uint64_t* sent = nullptr;       // (list start << 24 | list length) per (set, list) record
@@ -1295,7 +1290,7 @@ __global__ __launch_bounds__(256) void sparse_reduce_kernel(const int32_t* __res
             I[(i - r0) * ldI + (j - c0)] = v;
             const int64_t na = soff[i + 1] - soff[i], nb = soff[j + 1] - soff[j];
             double d;
-            if (v > 0) d = 1.0 - (double)v / (double)(na + nb - v);      // as epilogue_kernel (bitset.hip)
+            if (v > 0) d = 1.0 - (double)v / (double)(na + nb - v);      // as epilogue_kernel (matrix_step.hip)
             else d = (empty_nan && na + nb == 0) ? __builtin_nan("") : 1.0;
             D[(i - r0) * ldD + (j - c0)] = d;
         } else if (v) {

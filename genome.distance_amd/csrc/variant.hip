@@ -64,11 +64,6 @@
 namespace gdist {
 namespace {
 
-inline int grid_for(int64_t n, int block = 256, int64_t cap = 256 * 32) {
-    int64_t g = ceil_div(n, block);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
-
 __device__ __forceinline__ int64_t lower_bound_u64(const uint64_t* __restrict__ a, int64_t lo, int64_t hi, uint64_t k) {
     while (lo < hi) {
         const int64_t mid = (lo + hi) >> 1;
@@ -334,7 +329,7 @@ __global__ void combine_perm_kernel(const int32_t* __restrict__ dense, const int
 }
 
 // ---- the hash fill --------------------------------------------------------
-// The windowed fill (bitset.hip fill_pos_kernel) stages a stretch of the
+// The windowed fill (bitset_fill.hip fill_pos_kernel) stages a stretch of the
 // sorted dictionary per segment of a set's codes: made for dictionaries about
 // the size of a set (C2: 4 M each). C4's dictionary of kmers held by >= 2
 // sets is 377 M codes against 200 K per set, so every segment's windows spill
@@ -802,7 +797,7 @@ __global__ __launch_bounds__(256) void variant_query_kernel(const int64_t* __res
 // Short-list walk of a grouped rare tier (round 5; C3: 22.7 M entries whose
 // word lists hold ~20 sets). The wave-per-entry walk above leaves most of a
 // wave's 64 lanes idle on such lists; here, as in the rare tier's row walk
-// (bitset.hip rare_rows_kernel), a thread takes one entry of the row and
+// (rare.hip rare_rows_kernel), a thread takes one entry of the row and
 // walks its list from the row's own position (upper triangle) four packed
 // members (set | mask << 16) a 16-byte load, adding popc(mask_i & mask_j)
 // into LDS counters of one column chunk; lists of kLongList+ entries are
@@ -1096,7 +1091,7 @@ static CodeGeom code_geom(const gdist_sets* s) {
 // The fill by hash probes (above): dense bits, rare records (rank << 32 |
 // set + id_base) and, through the hook, the variant records of every chunk of
 // sets. The variant build's fill, and the two-tier build's when the sets are
-// sparse against the dictionary (bitset.hip fill_bits: C3)
+// sparse against the dictionary (bitset_fill.hip fill_bits: C3)
 void hash_fill(gdist_ctx* ctx, const gdist_sets* s, const uint64_t* dict, int64_t U, const uint32_t* perm,
                const uint64_t* rare, int64_t Ur, int64_t W, unsigned long long* bits, int64_t id_base,
                unsigned long long* rare_out, int64_t rare_cap, int64_t* rare_written, const FillHook& hook,

@@ -46,7 +46,7 @@ constexpr int kLoads = 4;                    // 64-column loads a lane has in fl
 constexpr int kSegCols = 64 * kLoads * 2;    // columns of a tile
 
 // The test of one (row q, column c0 + b) cell, b < nc.
-//  FromCounts: d is the Java expression of epilogue_kernel (bitset.hip) and
+//  FromCounts: d is the Java expression of epilogue_kernel (matrix_step.hip) and
 //  closest_select_kernel from I, fp64, no contraction; else d is loaded from D.
 //  The row's size comes from roff, the column's from coff: one collection
 //  passes the same pointer twice, gdist_cross_within the queries' and the

@@ -58,19 +58,12 @@ _REPO = os.path.dirname(_PKG)
 
 def tree_source_hash() -> str:
     """sha256 prefix of the library's sources in this tree, in the Makefile's
-    order (csrc/*.hip by name, csrc/gdist_internal.hpp, csrc/sparse_bounds.hpp,
-    csrc/group_stats_host.hpp, csrc/cross_plan.hpp, csrc/sketch_cross_merge.hpp,
-    csrc/sketch_wave_merge.hpp, csrc/pair_list.hpp, csrc/cross_cut.hpp,
-    csrc/sparse_triple.hpp, include/gdist.h)."""
+    order: csrc/*.hip by name, then csrc/*.hpp by name, then include/gdist.h."""
     import glob
     import hashlib
     files = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hip")))
-    files += [os.path.join(_PKG, "csrc", "gdist_internal.hpp"), os.path.join(_PKG, "csrc", "sparse_bounds.hpp"),
-              os.path.join(_PKG, "csrc", "group_stats_host.hpp"), os.path.join(_PKG, "csrc", "cross_plan.hpp"),
-              os.path.join(_PKG, "csrc", "sketch_cross_merge.hpp"), os.path.join(_PKG, "csrc", "sketch_wave_merge.hpp"),
-              os.path.join(_PKG, "csrc", "pair_list.hpp"), os.path.join(_PKG, "csrc", "cross_cut.hpp"),
-              os.path.join(_PKG, "csrc", "sparse_triple.hpp"),
-              os.path.join(_REPO, "include", "gdist.h")]
+    files += sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hpp")))
+    files.append(os.path.join(_REPO, "include", "gdist.h"))
     h = hashlib.sha256()
     for f in files:
         with open(f, "rb") as fh:

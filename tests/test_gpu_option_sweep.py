@@ -39,9 +39,9 @@ CSRC = os.path.join(ROOT, "genome.distance_amd", "csrc")
 
 N = 300
 CUS = 256                         # compute units of an MI355X (the gpu marker's device): ctx->cus
-BT = 128                          # bitset.hip: tile edge of the AND + popcount tiles
+BT = 128                          # bitset_tiles.hpp: tile edge of the AND + popcount tiles
 KC2 = 8                           # bitset.hip: words a chunk of those tiles
-PARTIAL_MAX_RR = 6                # bitset.hip: kPartialMaxRR
+PARTIAL_MAX_RR = 6                # bitset_tiles.hpp: kPartialMaxRR
 # (r0, r1, c0, c1, upper): the whole triangle, a row block that straddles the
 # diagonal, a rectangle off every tile bound
 REGIONS = [(0, 300, 0, 300, True), (129, 260, 0, 300, True), (37, 201, 5, 290, False)]
@@ -195,7 +195,7 @@ def assert_families(tag, ms, ran):
 
 def dense_launch_tiles(r0, r1, c0, c1, upper, split_diag, max_rr=PARTIAL_MAX_RR):
     """Tiles of the AND + popcount launches of a region, as matrix_plan groups
-    them (bitset.hip): off-diagonal, diagonal, partial off-diagonal, partial
+    them (matrix_step.hip, matrix_plan): off-diagonal, diagonal, partial off-diagonal, partial
     diagonal."""
     nr = r1 - r0
     tr = -(-nr // BT)
@@ -213,7 +213,7 @@ def dense_launch_tiles(r0, r1, c0, c1, upper, split_diag, max_rr=PARTIAL_MAX_RR)
 
 
 def k_splits(tW, nt, wg_per_cu, min_chunks):
-    """sp2 of one launch of nt tiles (bitset.hip, `launch` in bitset_matrix)."""
+    """sp2 of one launch of nt tiles (bitset.hip, `launch` in dense_tiles_launch)."""
     nch2 = tW // KC2
     return max(1, min(max(1, nch2 // max(1, min_chunks)), -(-CUS * max(1, wg_per_cu) // nt)))
 
@@ -262,7 +262,7 @@ def test_option_values_exact(ctx, opts, base, o, kind):
     ws, wd, _ = sets.sparse_info()
     W = sets.bitset_info()[1]
     if kind == "diag":
-        # bitset.hip, matrix_plan: `split_diag = upper && bitset_diag != 0`;
+        # matrix_step.hip, matrix_plan: `split_diag = upper && bitset_diag != 0`;
         # 0 keeps corg = c0 and no DIAG group, so the diagonal tiles run in
         # the ordinary launch (with bitset_mfma default and >= 64 dense words
         # the MFMA tiles run instead and the option only moves the plan key)
@@ -270,7 +270,7 @@ def test_option_values_exact(ctx, opts, base, o, kind):
         assert dense_launch_tiles(0, N, 0, N, True, True)[1::2] == [2, 1]
         assert_families(tag, ms, {"dense", "rare"} | ({"sparse"} if ws else set()))
     elif kind.startswith("ksplit"):
-        # bitset.hip, bitset_matrix `launch`: sp2 from bitset_wg_per_cu and
+        # bitset.hip, dense_tiles_launch `launch`: sp2 from bitset_wg_per_cu and
         # bitset_min_chunks over the launches of the whole triangle
         tW = wd if ws else W
         nch2 = tW // KC2
@@ -286,7 +286,7 @@ def test_option_values_exact(ctx, opts, base, o, kind):
             assert all(1 < x < nch2 and nch2 % x != 0 for x in sp), (tag, sp)
         assert_families(tag, ms, {"dense", "rare"})
     elif kind == "partial":
-        # bitset.hip, matrix_plan: `p.part = p.rr <= max_rr`. The whole
+        # matrix_step.hip, matrix_plan: `p.part = p.rr <= max_rr`. The whole
         # triangle's last row tile holds 44 rows (RR 3: launches of its own
         # unless bitset_partial_rr < 3); 240 rows leave 112 (RR 7: launches of
         # its own only with bitset_partial_rr 7)
@@ -301,15 +301,15 @@ def test_option_values_exact(ctx, opts, base, o, kind):
         check_region(tag, I, D, eI, eD, 7, 247, 3, 290, False)
         assert_families(tag, ms, {"dense", "rare"})
     elif kind == "order":
-        # bitset.hip, bitset_matrix: `dense_first` decides whether
+        # matrix_step.hip, bitset_matrix: `dense_first` decides whether
         # launch_side runs before or after the dense tiles' launch
         assert_families(tag, ms, {"dense", "rare"} | ({"sparse"} if ws else {"variant"}))
     elif kind == "summary":
-        # bitset.hip, build: `by_range = rs_opt > 0 || ...`: range_summary
+        # bitset_build.hip, build_bitsets: `by_range = rs_opt > 0 || ...`: range_summary
         # instead of local_summary, at a size the default never takes it
         assert_families(tag, ms, {"sparse"})
     elif kind == "rare_inline":
-        # bitset.hip, bitset_matrix: `overlap` / `rows_side` false, so the
+        # matrix_step.hip, bitset_matrix: `overlap` / `rows_side` false, so the
         # rare kernel (list-major rare_pairs_kernel with rare_kernel 0, the
         # LDS-flushing rare_rows_kernel with 1) is issued on the main stream
         # after the join, with no fork of its own. The library cannot show
@@ -321,7 +321,7 @@ def test_option_values_exact(ctx, opts, base, o, kind):
         assert ctx.last_timing()[2] == 2, (tag, ctx.last_timing())
         assert_families(tag, ms, {"rare", "sparse" if ws else "dense"})
     elif kind == "serial":
-        # bitset.hip, bitset_matrix: `serial` puts launch_side on the main
+        # matrix_step.hip, bitset_matrix: `serial` puts launch_side on the main
         # stream (sd = st) ahead of the dense tiles and forces dense_first off
         side = {"sparse"} if ws else {"variant"}
         assert_families(tag, ms, {"dense", "rare"} | side)
@@ -333,7 +333,7 @@ def test_option_values_exact(ctx, opts, base, o, kind):
         # the option are asserted by test_sparse_wg_per_cu_chunk_counts
         assert_families(tag, ms, {"sparse"})
     elif kind == "split_build":
-        # bitset.hip, build: range_summary = 0 asks for the one-sort summary;
+        # bitset_build.hip, build_bitsets: range_summary = 0 asks for the one-sort summary;
         # a split build's shares are code ranges
         assert sets.build_timing()["shares"] == o["split_build"], (tag, sets.build_timing())
         assert_families(tag, ms, {"sparse"})
@@ -393,7 +393,7 @@ def test_sparse_wg_per_cu_chunk_counts(ctx, opts, capfd, o):
             under = plan_counts(capfd.readouterr().err)
         check_region(o, I, D, eI, eD, r0, r1, c0, c1, up)
     # the same collection and region under the default target: another plan
-    # key (bitset.hip, matrix_plan), so the plan is built and reported again
+    # key (matrix_step.hip, matrix_plan), so the plan is built and reported again
     opts(sparse_wg_per_cu=None)
     capfd.readouterr()
     I, D = sets.matrix(upper=True, method=gdist.METHOD_BITSET)
