@@ -1254,6 +1254,38 @@ int gdist_greedy_reps(gdist_ctx* ctx, const gdist_sets* sets, int method, double
     });
 }
 
+int gdist_sketch_greedy_reps(gdist_ctx* ctx, const gdist_sets* sk, double max_dist, unsigned flags,
+                             const int64_t* tie_rank, int32_t* is_rep, int64_t* rep_of, double* rep_dist,
+                             int64_t* nreps) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_sets(sk);
+        GD_REQUIRE(sk->ctx == ctx, "sketches belong to another context");
+        GD_REQUIRE(sk->kind == GDIST_SKETCH, "not a sketch collection (gdist_greedy_reps takes kmer sets)");
+        check_codes(sk);
+        GD_REQUIRE(is_rep != nullptr, "is_rep is required");
+        GD_REQUIRE(!(flags & ~(GDIST_EMPTY_NAN | GDIST_SKETCH_JACCARD)),
+                   "gdist_sketch_greedy_reps takes no flag but GDIST_EMPTY_NAN and GDIST_SKETCH_JACCARD");
+        std::fill(ctx->reps_info, ctx->reps_info + 4, (int64_t)0);
+        if (sk->nsets == 0) {
+            if (nreps) *nreps = 0;
+            return;
+        }
+        ctx->pending = false;          // an unread previous call's times are dropped, not waited for
+        ctx->last = Timing{};
+        gdist::sketch_greedy_reps(ctx, sk, max_dist, flags, tie_rank, is_rep, rep_of, rep_dist, nreps);
+    });
+}
+
+int gdist_ctx_reps_info(gdist_ctx* ctx, int64_t out[4]) {
+    return guard([&] {
+        GD_REQUIRE(ctx != nullptr && out != nullptr, "null argument");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        std::copy(ctx->reps_info, ctx->reps_info + 4, out);
+    });
+}
+
 int gdist_row_query(gdist_ctx* ctx, const gdist_sets* sets, int64_t q, const int64_t* cols, int64_t ncols, int mode,
                     double t, double* D_out, int32_t* hit, int64_t* best_idx, double* best_d) {
     return guard([&] {

@@ -408,6 +408,9 @@ struct gdist_ctx {
     // and the work units launched
     double cross_join_ms = -1.0, cross_select_ms = -1.0;
     int64_t cross_units = 0;
+    // the last gdist_sketch_greedy_reps call (gdist_ctx_reps_info): pass-1 row blocks, the (row,
+    // representative) cells its column-list launches covered in pass 1 and in pass 2, those launches
+    int64_t reps_info[4] = {0, 0, 0, 0};
     gdist_ctx() { for (auto& o : opt) o = gdist::kOptUnset; }
     int64_t option(gdist::Opt o, int64_t dflt) const { return opt[o] == gdist::kOptUnset ? dflt : opt[o]; }
     bool has_option(gdist::Opt o) const { return opt[o] != gdist::kOptUnset; }
@@ -1093,6 +1096,15 @@ void lsh_closest(gdist_ctx* ctx, const gdist_lsh* L, const gdist_sets* qs, int n
 void sketch_build(gdist_ctx* ctx, const gdist_sets* s, int width, gdist_sets* out);
 void sketch_matrix(gdist_ctx* ctx, const gdist_sets* sk, int64_t r0, int64_t r1, int64_t c0,
                    int64_t c1, unsigned flags, int32_t* d_common, double* d_D, int64_t ld);
+// rows [r0, r1) x the sketches d_cols[0 .. ncols) (device: set indices, any order) through the ring
+// kernel over a column list: d_D / d_common are [r1 - r0][ld], column p the distance to d_cols[p], each
+// cell sketch_matrix's for (row, d_cols[p]). flags: GDIST_EMPTY_NAN, GDIST_SKETCH_JACCARD. Returns launches
+int sketch_matrix_cols(gdist_ctx* ctx, const gdist_sets* sk, int64_t r0, int64_t r1, const int64_t* d_cols,
+                       int64_t ncols, unsigned flags, int32_t* d_common, double* d_D, int64_t ld);
+// sketch_reps.hip — gdist_sketch_greedy_reps: every argument checked by the caller, nsets > 0,
+// ctx->reps_info zeroed; host outputs as greedy_reps
+void sketch_greedy_reps(gdist_ctx* ctx, const gdist_sets* sk, double t, unsigned flags, const int64_t* tie_rank,
+                        int32_t* is_rep, int64_t* rep_of, double* rep_dist, int64_t* nreps);
 
 __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // blocks of a grid-stride launch over n elements, at least 1 and at most cap

@@ -538,6 +538,202 @@ __global__ __launch_bounds__(kSkTile * kSkTile) void sketch_ring_kernel(
     if (D) D[o] = d;
 }
 
+// The ring kernel over a column list: rows [r0, r1) a range, columns the
+// sketches cols[0 .. ncols) (set indices, any order). sketch_ring_kernel's
+// code (its comments apply line for line) with the four places that name a
+// column changed: slot s - R of column tile tcb holds sketch cols[32 tcb +
+// (s - R)] while that position is < ncols; no triangle (upper and tri are
+// gone); a pair's column j and its output column are positions in the list,
+// the set index appears in off[...] only (the ring top-up and the
+// global-memory steps read through s_base). A copy and not a shared body:
+// moved into a forced-inline template the range kernel compiled to other
+// instructions (profiles/r13/kernel_isa.txt compares it with its parent).
+__global__ __launch_bounds__(kSkTile * kSkTile) void sketch_ring_cols_kernel(
+    const int32_t* __restrict__ sig, const int64_t* __restrict__ off, int width, int RS, int kmax, int64_t r0,
+    int64_t r1, const int64_t* __restrict__ cols, int64_t ncols, int64_t tile0, int tiles_c, int jaccard,
+    int empty_nan, int32_t* __restrict__ common_out, double* __restrict__ D, int64_t ld, int fallback, int sperm) {
+#pragma clang fp contract(off)
+    constexpr int R = kSkTile, C = kSkTile, NT = R * C, NW = NT / 64, NS = kSkLanes;
+    extern __shared__ __attribute__((aligned(16))) int32_t sm[];
+    int64_t* s_base = reinterpret_cast<int64_t*>(sm + (RS + 1) * NS);     // 8-byte aligned: 256 B a ring row
+    int32_t* s_n = reinterpret_cast<int32_t*>(s_base + NS);
+    int32_t* s_top = s_n + NS;
+    int32_t* s_min = s_top + NS;
+    int32_t* s_imax = s_min + NS;
+    int32_t* s_or = s_imax + NS;                                           // block_or's three flag words
+    const uint32_t ring0 = (uint32_t)(size_t)(const lds_i32*)sm;
+    const int64_t bt = tile0 + blockIdx.x;
+    const int tr = (int)(bt / tiles_c), tcb = (int)(bt % tiles_c);
+    const int64_t row0 = r0 + (int64_t)tr * R, col0 = (int64_t)tcb * C;     // col0: a position in cols
+    const int g = threadIdx.x >> 5, l = threadIdx.x & 31;
+    const int ty = l, tx = (l + g) & (C - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (threadIdx.x < NS) {
+        const int s = threadIdx.x;
+        const int64_t p = s < R ? row0 + s : col0 + (s - R);
+        const bool ok = s < R ? p < r1 : p < ncols;
+        const int64_t gi = s < R || !ok ? p : cols[p];                    // the set index: read here only
+        const int64_t b = ok ? off[gi] : 0;
+        const int n = ok ? (int)(off[gi + 1] - b) : 0;
+        s_base[s] = b;
+        s_n[s] = n;
+        s_top[s] = 0;
+        s_imax[s] = n > 0 && sig[b + n - 1] == 0x7FFFFFFF;
+        if (s < 3) s_or[s] = 0;
+    }
+    __syncthreads();
+    int orc = 0;
+    auto block_or = [&](bool v) -> bool {
+        const int k = orc % 3;
+        if (v) s_or[k] = 1;
+        if (threadIdx.x == 0) s_or[k == 2 ? 0 : k + 1] = 0;
+        __syncthreads();
+        const bool r = s_or[k] != 0;
+        orc++;
+        return r;
+    };
+    const int64_t i = row0 + ty, j = col0 + tx;
+    const bool valid = i < r1 && j < ncols;
+    const int ina = s_n[ty], inb = s_n[R + tx];
+    const bool imax = s_imax[ty] || s_imax[R + tx];
+    const int lim = jaccard ? ina + inb : width;
+    int ia = 0, ib = 0, steps = 0, extra = 0;
+    bool open = valid;
+    if (open && (ina == 0 || inb == 0 || lim == 0)) {
+        extra = min(ina + inb, lim);
+        open = false;
+    }
+    const int32_t* Arow = sm + ty;
+    const int32_t* Brow = sm + R + tx;
+    const int32_t* gA = sig + s_base[ty];
+    const int32_t* gB = sig + s_base[R + tx];
+    bool stalled = false;
+    for (;;) {
+        if (threadIdx.x < NS) s_min[threadIdx.x] = 0x7FFFFFFF;
+        __syncthreads();
+        if (open) {
+            atomicMin(&s_min[ty], ia);
+            atomicMin(&s_min[R + tx], ib);
+        }
+        __syncthreads();
+        {
+            const int s = lane;
+            const int n = s_n[s], least = s_min[s];
+            const int lo = least == 0x7FFFFFFF ? 0 : max(s_top[s], least);
+            const int hi = least == 0x7FFFFFFF ? 0 : min(n + 2, least + RS);
+            const int32_t* src = sig + s_base[s];
+            const int M = RS - 1;                   // RS: a power of two
+            int q = (lo + wave * 4) & M;
+            for (int t = lo + wave * 4; t < hi; t += NW * 4) {
+                i32x4_a4 v;
+                if (t + 4 <= n) {
+                    v = *reinterpret_cast<const i32x4_a4*>(src + t);
+                } else {
+                    v.x = t < n ? src[t] : 0x7FFFFFFF;
+                    v.y = t + 1 < n ? src[t + 1] : 0x7FFFFFFF;
+                    v.z = t + 2 < n ? src[t + 2] : 0x7FFFFFFF;
+                    v.w = 0x7FFFFFFF;
+                }
+                const int32_t vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    if (t + u < hi) {
+                        const int qu = (q + u) & M;
+                        sm[qu * NS + s] = vv[u];
+                        if (qu == 0) sm[RS * NS + s] = vv[u];
+                    }
+                }
+                q = (q + NW * 4) & M;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < NS && s_min[threadIdx.x] != 0x7FFFFFFF)
+            s_top[threadIdx.x] = min(s_n[threadIdx.x] + 2, s_min[threadIdx.x] + RS);
+        int done = 0;
+        if (open) {
+            const int roomA = min(s_n[ty] + 2, s_min[ty] + RS) - ia;
+            const int roomB = min(s_n[R + tx] + 2, s_min[R + tx] + RS) - ib;
+            const int K = min(min(kmax, lim - steps), min(roomA, roomB));
+            if (K > 0) {
+                const int mask = RS - 1;
+                int pa = ia, pb = ib;
+                while (!imax) {
+                    const int ns = min(K - done, max(ina - pa, inb - pb));
+                    if (ns < 2) break;
+                    const int nr = ns >> 1;
+                    if (RS == 256 && sperm && ring0 == 0) {
+                        const uint32_t ra = 4u * (uint32_t)ty, rb = 4u * (uint32_t)(R + tx);
+                        for (int r = 0; r < nr; r++) {
+                            const lds_i32* pA = (const lds_i32*)(size_t)__builtin_amdgcn_perm((uint32_t)pa, ra, 0x0C0C0400u);
+                            const lds_i32* pB = (const lds_i32*)(size_t)__builtin_amdgcn_perm((uint32_t)pb, rb, 0x0C0C0400u);
+                            const int32_t a0 = pA[0], a1 = pA[NS], b0 = pB[0], b1 = pB[NS];
+                            const bool le = a0 <= b0, ge = b0 <= a0;
+                            const int32_t x = le ? a1 : a0, y = ge ? b1 : b0;
+                            pa += le;
+                            pb += ge;
+                            pa += x <= y;
+                            pb += y <= x;
+                        }
+                    } else {
+                        for (int r = 0; r < nr; r++) {
+                            const int32_t* pA = Arow + (pa & mask) * NS;      // slot RS - 1: pA[NS] is the mirror row
+                            const int32_t* pB = Brow + (pb & mask) * NS;
+                            const int32_t a0 = pA[0], a1 = pA[NS], b0 = pB[0], b1 = pB[NS];
+                            const bool le = a0 <= b0, ge = b0 <= a0;
+                            const int32_t x = le ? a1 : a0, y = ge ? b1 : b0;
+                            pa += le;
+                            pb += ge;
+                            pa += x <= y;
+                            pb += y <= x;
+                        }
+                    }
+                    done += 2 * nr;
+                }
+                while (done < K && pa < ina && pb < inb) {            // checked steps inside the rings
+                    const int32_t va = Arow[(pa & mask) * NS], vb = Brow[(pb & mask) * NS];
+                    pa += va <= vb;
+                    pb += vb <= va;
+                    done++;
+                }
+                ia = pa;
+                ib = pb;
+            } else if (stalled || fallback) {
+                const int Kg = min(kmax, lim - steps);
+                while (done < Kg && ia < ina && ib < inb) {
+                    const int32_t va = gA[ia], vb = gB[ib];
+                    ia += va <= vb;
+                    ib += vb <= va;
+                    done++;
+                }
+            }
+            steps += done;
+            if (steps >= lim) open = false;
+            else if (ia == ina || ib == inb) {     // a side ended: the rest are union-only
+                extra = min((ina - ia) + (inb - ib), lim - steps);
+                open = false;
+            }
+        }
+        stalled = !block_or(done > 0);
+        if (!block_or(open)) break;
+    }
+    if (!valid) return;
+    const int common = ia + ib - steps;
+    const int taken = steps + extra;
+    const int64_t na = ina, nb = inb;
+    double d;
+    if (jaccard) {
+        if (common > 0) d = 1.0 - (double)common / (double)(na + nb - common);
+        else d = (empty_nan && na + nb == 0) ? __builtin_nan("") : 1.0;
+    } else {
+        if (common > 0) d = 1.0 - (double)common / (double)taken;
+        else d = (empty_nan && taken == 0) ? __builtin_nan("") : 1.0;
+    }
+    const int64_t o = (i - r0) * ld + j;
+    if (common_out) common_out[o] = (int32_t)common;
+    if (D) D[o] = d;
+}
+
+
 template <int R, int C>
 constexpr size_t sketch_meta_bytes() { return (size_t)(R + C) * (sizeof(int64_t) + sizeof(int32_t)); }
 
@@ -567,6 +763,33 @@ int launch_sketch_ring(hipStream_t st, const gdist_sets* sk, int width, int rs, 
         kern<<<(unsigned)std::min(per, grid - t0), threads, lds, st>>>(
             sk->codes.as<int32_t>(), sk->off.as<int64_t>(), width, rs, kmax, r0, r1, c0, c1, t0, tc, upper, jac, en,
             d_common, d_D, ld, fallback ? 1 : 0, tri ? 1 : 0, sperm ? 1 : 0);
+    GD_HIP(hipGetLastError());
+    return launches;
+}
+
+// The ring kernel over a column list: rows [r0, r1) x the sketches
+// d_cols[0 .. ncols) (device, set indices of sk, any order, repeats allowed)
+// into d_D / d_common, [r1 - r0][ld], column p the list's position p.
+int launch_sketch_ring_cols(hipStream_t st, const gdist_sets* sk, int width, int rs, int kmax, int64_t r0, int64_t r1,
+                             const int64_t* d_cols, int64_t ncols, int jac, int en, int32_t* d_common, double* d_D,
+                             int64_t ld, bool fallback, bool sperm) {
+    const size_t lds = sketch_ring_lds(rs);
+    GD_REQUIRE(rs >= 16 && (rs & (rs - 1)) == 0 && kmax >= 2 && kmax < rs,
+               "sketch ring: a power of two >= 16 slots, 2 <= steps per phase < slots");
+    GD_REQUIRE(lds + 64 <= (size_t)LDS_SK_MAX, "sketch ring exceeds LDS");
+    GD_REQUIRE(ld >= ncols, "leading dimension smaller than the column list");
+    const int tr = (int)ceil_div(r1 - r0, kSkTile), tc = (int)ceil_div(ncols, kSkTile);
+    const int64_t grid = (int64_t)tr * tc;
+    const int threads = kSkTile * kSkTile;
+    const int64_t per = (int64_t(1) << 31) / threads;     // a dispatch holds < 2^32 work-items
+    auto kern = &sketch_ring_cols_kernel;
+    GD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lds));
+    int launches = 0;
+    for (int64_t t0 = 0; t0 < grid; t0 += per, launches++)
+        kern<<<(unsigned)std::min(per, grid - t0), threads, lds, st>>>(
+            sk->codes.as<int32_t>(), sk->off.as<int64_t>(), width, rs, kmax, r0, r1, d_cols, ncols, t0, tc, jac, en,
+            d_common, d_D, ld, fallback ? 1 : 0, sperm ? 1 : 0);
     GD_HIP(hipGetLastError());
     return launches;
 }
@@ -754,6 +977,23 @@ void sketch_matrix(gdist_ctx* ctx, const gdist_sets* sk, int64_t r0, int64_t r1,
     }
     GD_HIP(hipEventRecord(ctx->ev_k1, st));
     ctx->last.launches = launches;
+}
+
+// Reads the ring options sketch_matrix reads (sketch_cap, sketch_ring,
+// sketch_wait, sketch_perm), with its defaults. sketch_phase, sketch_tile and
+// sketch_k select other kernels for sketch_matrix and do not apply here: a
+// column list always takes the ring kernel (it streams the signatures, so any
+// width fits).
+int sketch_matrix_cols(gdist_ctx* ctx, const gdist_sets* sk, int64_t r0, int64_t r1, const int64_t* d_cols,
+                       int64_t ncols, unsigned flags, int32_t* d_common, double* d_D, int64_t ld) {
+    if (r1 - r0 <= 0 || ncols <= 0) return 0;
+    const int jac = (flags & GDIST_SKETCH_JACCARD) ? 1 : 0, en = (flags & GDIST_EMPTY_NAN) ? 1 : 0;
+    const int width = std::max(1, sk->width);
+    const int kmax = (int)std::max<int64_t>(2, std::min<int64_t>(ctx->option(OPT_SKETCH_CAP, 160), 1 << 20));
+    const int rs = (int)std::max<int64_t>(16, std::min<int64_t>(ctx->option(OPT_SKETCH_RING, 256), 1 << 20));
+    return launch_sketch_ring_cols(ctx->stream, sk, width, rs, std::min(kmax, rs - 1), r0, r1, d_cols, ncols, jac, en,
+                                   d_common, d_D, ld, ctx->option(OPT_SKETCH_WAIT, 0) == 0,
+                                   ctx->option(OPT_SKETCH_PERM, 1) != 0);
 }
 
 }  // namespace gdist

@@ -143,6 +143,8 @@ _SIGS = {
     "gdist_sketch_download": (C.c_int, [_setp, _i64p, _i32p]),
     "gdist_sketch_matrix": (C.c_int, [_ctxp, _setp, _i64, _i64, _i64, _i64, _u32, _vp, _vp, _i64]),
     "gdist_sketch_pairs": (C.c_int, [_ctxp, _setp, _setp, _i64, _i64p, _i64p, _u32, _i32p, _dblp]),
+    "gdist_sketch_greedy_reps": (C.c_int, [_ctxp, _setp, _dbl, _u32, _i64p, _i32p, _i64p, _dblp, _i64p]),
+    "gdist_ctx_reps_info": (C.c_int, [_ctxp, _i64p]),
     "gdist_lsh_build": (C.c_int, [_ctxp, _setp, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]),
     "gdist_lsh_free": (C.c_int, [C.c_void_p]),
     "gdist_lsh_closest": (C.c_int, [_ctxp, C.c_void_p, _setp, C.c_int, _dbl, _i64p, _dblp, _i32p]),

@@ -161,6 +161,15 @@ class Context:
         L.check(L.lib.gdist_ctx_cross_info(self.h, C.byref(j), C.byref(s), C.byref(u)))
         return j.value, s.value, u.value
 
+    def reps_info(self) -> tuple[int, int, int, int]:
+        """The context's last SketchSets.greedy_reps() call (gdist_ctx_reps_info):
+        (row blocks of pass 1, (row, representative) cells the column-list
+        launches covered in pass 1, the same for pass 2 (0 without assign),
+        column-list launches). Zeros before any such call."""
+        out = (C.c_int64 * 4)()
+        L.check(L.lib.gdist_ctx_reps_info(self.h, out))
+        return tuple(int(v) for v in out)
+
     def step_info(self) -> tuple[int, int, int, int]:
         """How the context's repeated matrix_device() calls went out so far
         (gdist_ctx_step_info): (fused sparse steps issued pipelined over the
@@ -1378,6 +1387,32 @@ class SketchSets(_Handle):
         cl = np.ascontiguousarray(np.fromiter(cols, dtype=np.int64))
         _, D = self.pairs(np.full(len(cl), q, dtype=np.int64), cl, other=other, want_common=False)
         return reduce_row_query(D, mode, t)
+
+    def greedy_reps(self, max_dist: float, assign: bool = False, tie_rank: np.ndarray | None = None,
+                    flags: int = 0):
+        """Greedy representatives of the signatures on the device
+        (gdist_sketch_greedy_reps), d the sketch distance matrix() returns under
+        `flags` (SKETCH_JACCARD, EMPTY_NAN). Returns what KmerSets.greedy_reps
+        returns: is_rep (int32[N]); with assign=True also (rep_of int64[N],
+        rep_dist float64[N]), ties to the lowest tie_rank (default: index).
+        Context.reps_info() reports the call."""
+        n = len(self)
+        is_rep = np.zeros(max(n, 1), dtype=np.int32)
+        nreps = C.c_int64()
+        rep_of = np.zeros(max(n, 1), dtype=np.int64) if assign else None
+        rep_d = np.zeros(max(n, 1), dtype=np.float64) if assign else None
+        tr = None
+        if tie_rank is not None:
+            tr = np.ascontiguousarray(tie_rank, dtype=np.int64)
+            assert tr.shape == (n,)
+        L.check(L.lib.gdist_sketch_greedy_reps(self.ctx.h, self.h, float(max_dist), int(flags),
+                                               L.ptr(tr, C.c_int64) if tr is not None else None,
+                                               L.ptr(is_rep, C.c_int32),
+                                               L.ptr(rep_of, C.c_int64) if assign else None,
+                                               L.ptr(rep_d, C.c_double) if assign else None, C.byref(nreps)))
+        if assign:
+            return is_rep[:n], rep_of[:n], rep_d[:n]
+        return is_rep[:n]
 
     def matrix_device(self, d_common: int | None, d_D: int | None, ld: int, rows, cols, upper=False, flags=0):
         fl = flags | L.OUT_DEVICE | (L.UPPER_TRIANGLE if upper else 0)

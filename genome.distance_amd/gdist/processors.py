@@ -200,20 +200,33 @@ def _greedy_host(sets: KmerSets, keys: Sequence[str], max_dist: float) -> list[i
     return list(rep_of_key.values())
 
 
-def _greedy(sets: KmerSets, keys: Sequence[str], max_dist: float) -> list[int]:
-    """Pass 1: on the device when keys are unique (gdist_greedy_reps),
-    otherwise the host loop with HashMap.put replacement."""
+def _greedy(sets, keys: Sequence[str], max_dist: float) -> list[int]:
+    """Pass 1: on the device when keys are unique (gdist_greedy_reps; on
+    sketches gdist_sketch_greedy_reps), otherwise the host loop with
+    HashMap.put replacement. `sets`: KmerSets or SketchSets."""
     if len(set(keys)) == len(keys):
         is_rep = sets.greedy_reps(max_dist)
         return [int(i) for i in np.flatnonzero(is_rep)]
     return _greedy_host(sets, keys, max_dist)
 
 
+def _sketched(sets: KmerSets, width: int):
+    """The sets' MinHash sketches of `width`; the kmer sets are freed, since
+    the selection reads the signatures only."""
+    try:
+        return sets.sketches(width)
+    finally:
+        sets.free()
+
+
 def fasta_reps(records: Sequence[FastaRecord], out: TextIO, kmer_size: int = 0, max_dist: float = 0.97,
-               kmer_type: KmerType = KmerType.DNA, flags: int = 0, ctx: Context | None = None) -> list[int]:
+               kmer_type: KmerType = KmerType.DNA, flags: int = 0, ctx: Context | None = None,
+               sketch_width: int = 0) -> list[int]:
     """fastaReps (FastaDistanceRepsProcessor.java:111-149): greedy
     representatives in input order; one output line per new representative
-    (a repeated label re-enters repMap under its key and is printed again)."""
+    (a repeated label re-enters repMap under its key and is printed again).
+    sketch_width > 0: the selection runs on the sequences' MinHash sketches of
+    that width, d the sketch distance (0: on the kmer sets, as the reference)."""
     k = kmer_size or kmer_type.getKmerSize()
     if k < 2:
         raise ParseFailureException("Kmer size must be at least 2.")           # FastaDistanceRepsProcessor.java:84-85
@@ -221,6 +234,8 @@ def fasta_reps(records: Sequence[FastaRecord], out: TextIO, kmer_size: int = 0, 
     if not records:
         return []
     sets = KmerSets.from_sequences([r.sequence for r in records], k, kmer_type, flags, ctx)
+    if sketch_width > 0:
+        sets = _sketched(sets, sketch_width)
     labels = [r.label for r in records]
     if len(set(labels)) == len(labels):
         reps = _greedy(sets, labels, max_dist)
@@ -241,17 +256,21 @@ def fasta_reps(records: Sequence[FastaRecord], out: TextIO, kmer_size: int = 0, 
 
 
 def distance_reps(genomes: Sequence[Genome], kmer_size: int = 9, max_dist: float = 0.97, flags: int = 0,
-                  ctx: Context | None = None) -> tuple[str, str, str]:
+                  ctx: Context | None = None, sketch_width: int = 0) -> tuple[str, str, str]:
     """distReps (DistanceRepsProcessor.java:140-275): returns (file name
     prefix, list.tbl text, stats.tbl text). Pass 1 picks representatives in
     input order; pass 2 assigns every genome its closest representative,
-    ties to the earlier one in repMap's HashMap iteration order."""
+    ties to the earlier one in repMap's HashMap iteration order.
+    sketch_width > 0: both passes run on the genomes' MinHash sketches of that
+    width, d the sketch distance (0: on the kmer sets, as the reference)."""
     if kmer_size < 4:
         raise ParseFailureException("Kmer size must be at least 4.")           # DistanceRepsProcessor.java:156-157
     if max_dist <= 0.0 or max_dist >= 1.0:
         raise ParseFailureException("Distance must be strictly between 0 and 1.")  # DistanceRepsProcessor.java:160-161
     prefix = "rep%.4f_K%d" % (max_dist, kmer_size)                              # DistanceRepsProcessor.java:212
     sets = KmerSets.from_sequences([g.kmer_text() for g in genomes], kmer_size, KmerType.DNA, flags, ctx)
+    if sketch_width > 0:
+        sets = _sketched(sets, sketch_width)
     ids = [g.id for g in genomes]
     reps = _greedy(sets, ids, max_dist)                                         # pass 1 (DistanceRepsProcessor.java:185-200)
     rep_set = set(reps)

@@ -28,6 +28,8 @@
  *                          list, beside the exact kmer column    MethodTableProcessor.java:258-276
  *                          the sketch-against-exact comparison
  *                          over chosen pairs                     WidthProcessor.java:183-192
+ *   gdist_sketch_greedy_reps the distReps / fastaReps selection with
+ *                          Sketch.distance as the distance       DistanceRepsProcessor.java:185-200,227-237
  *   gdist_closest          getClosest(kmers, n, maxDist), exhaustively
  *                          (every column, no LSH buckets)        MashProcessor.java:150, FindProcessor.java:110
  *                          --maxDist of the genomes table        GenomeProcessor.java:58-60,89
@@ -443,6 +445,43 @@ int  gdist_sketch_matrix(gdist_ctx* ctx, const gdist_sets* sk,
 int  gdist_sketch_pairs(gdist_ctx* ctx, const gdist_sets* a, const gdist_sets* b, int64_t npairs,
                         const int64_t* rows /* into a */, const int64_t* cols /* into b */, unsigned flags,
                         int32_t* common_out, double* D_out);
+/* Greedy representatives of a sketch collection: gdist_greedy_reps's contract
+ * (pass 1 DistanceRepsProcessor.java:185-200, pass 2 :227-237) with d the
+ * sketch distance, bit for bit gdist_sketch_matrix's cell under the same
+ * flags (GDIST_EMPTY_NAN and GDIST_SKETCH_JACCARD, no other).
+ * Pass 1: signatures in index order; signature k becomes a representative
+ * unless an earlier representative r has d(k, r) <= max_dist, a plain fp64
+ * comparison: NaN (an empty pair under GDIST_EMPTY_NAN) never covers, d == 1.0
+ * covers when max_dist >= 1.0. is_rep[k] = 1 / 0 for every k, *nreps = their
+ * number (nreps may be NULL).
+ * Pass 2, when rep_of or rep_dist is non-NULL: every signature's closest
+ * representative, the least (d, tie_rank[representative]) over the
+ * representatives with d < 1.0 (tie_rank NULL: the set index; NaN is never
+ * closest); a representative maps to itself at 0.0; -1 / 1.0 when none.
+ *
+ * Only distances to representatives, and those inside a row block, are
+ * computed: per row block the ring kernel runs over the list of the
+ * representatives chosen so far (a column list, not a range), a second kernel
+ * says which rows one of them covers, and the host resolves the order inside
+ * the block from the block's own tile. The row block is gdist_greedy_reps's
+ * (option "reps_block" overrides it); the ring follows the options
+ * "sketch_cap", "sketch_ring", "sketch_wait" and "sketch_perm" as
+ * gdist_sketch_matrix's ring does. The collection is only read. On several
+ * ranks a gathered or replicated collection is answered whole on every rank.
+ * nsets == 0: GDIST_OK, *nreps = 0, nothing else is touched.
+ * EINVAL, decided before any work (the outputs stay untouched): a null handle,
+ * a handle of another context, a collection of kmer sets (gdist_greedy_reps
+ * takes those), a null is_rep, any other flag. */
+int  gdist_sketch_greedy_reps(gdist_ctx* ctx, const gdist_sets* sk, double max_dist, unsigned flags,
+                              const int64_t* tie_rank, int32_t* is_rep, int64_t* rep_of, double* rep_dist,
+                              int64_t* nreps);
+/* The context's last gdist_sketch_greedy_reps call: out[0] the row blocks of
+ * pass 1, out[1] the (row, representative) cells its column-list launches
+ * covered in pass 1 (the sum over the blocks of rows x representatives chosen
+ * before the block), out[2] the same for pass 2 (nsets x representatives, 0
+ * when neither rep_of nor rep_dist was asked for), out[3] the column-list
+ * launches. Zeros before any such call. */
+int  gdist_ctx_reps_info(gdist_ctx* ctx, int64_t out[4]);
 
 /* ---- LSH bucket query (MashProcessor / FindProcessor) ------------------ */
 /* Index of a sketch collection: new LSHMemSeqHash(width, stages, buckets)
