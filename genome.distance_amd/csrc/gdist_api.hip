@@ -1638,6 +1638,46 @@ int gdist_group_stats(gdist_ctx* ctx, const gdist_sets* sets, int64_t r0, int64_
     });
 }
 
+int gdist_width_sweep(gdist_ctx* ctx, const gdist_sets* sets, const gdist_sets* sk, int nsizes, const int32_t* sizes,
+                      int method, unsigned flags, gdist_width_row* rows_out, int64_t* pairs) {
+    return guard([&] {
+        use_device(ctx);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        check_sets(sets);
+        check_codes(sk);
+        GD_REQUIRE(sets->ctx == ctx && sk->ctx == ctx, "sets belong to another context");
+        GD_REQUIRE(sets->kind != GDIST_SKETCH, "gdist_width_sweep: sets is a sketch collection (pass the kmer sets)");
+        GD_REQUIRE(sk->kind == GDIST_SKETCH, "gdist_width_sweep: sk is not a sketch collection");
+        GD_REQUIRE(sets->nsets == sk->nsets, "the kmer sets and their sketches differ in number");
+        GD_REQUIRE(nsizes >= 0 && nsizes <= GDIST_WIDTH_MAX_SIZES, "nsizes outside 0 .. GDIST_WIDTH_MAX_SIZES");
+        GD_REQUIRE(pairs && (nsizes == 0 || (sizes && rows_out)), "null sizes or output");
+        for (int k = 0; k < nsizes; k++)
+            GD_REQUIRE(sizes[k] >= 1 && (k == 0 || sizes[k - 1] < sizes[k]),
+                       "sketch sizes are not strictly increasing from 1 or more");
+        GD_REQUIRE(nsizes == 0 || sizes[nsizes - 1] <= sk->width, "a sketch size is above the width of sk");
+        GD_REQUIRE(!(flags & ~GDIST_SKETCH_JACCARD), "gdist_width_sweep takes no flag but GDIST_SKETCH_JACCARD");
+        check_method(sets, method);
+        check_column_keys(sets);
+        const int64_t n = sets->nsets;
+        // into locals first: a failure on the device leaves the outputs untouched too
+        std::vector<gdist_width_row> o((size_t)nsizes);
+        int64_t np = 0;
+        for (int k = 0; k < nsizes; k++) {
+            std::memset(&o[k], 0, sizeof(o[k]));
+            o[k].size = sizes[k];
+            for (int64_t i = 0; i < n; i++) o[k].dwarves += sk->h_off[i + 1] - sk->h_off[i] < sizes[k] ? 1 : 0;
+        }
+        if (n >= 2 && nsizes > 0) {
+            auto* s = const_cast<gdist_sets*>(sets);
+            const int m = rect_method(ctx, s, method, n, n);
+            begin_call(ctx);
+            gdist::width_sweep(ctx, s, sk, nsizes, sizes, m, flags, o.data(), &np);
+        }
+        std::copy(o.begin(), o.end(), rows_out);
+        *pairs = np;
+    });
+}
+
 int gdist_group_stats_merge(gdist_group_side* acc, int64_t* bad_acc, const gdist_group_side* part,
                             const int64_t* bad_part, int ntypes) {
     return guard([&] {

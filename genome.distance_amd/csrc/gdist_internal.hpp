@@ -1006,6 +1006,13 @@ void group_stats(gdist_ctx* ctx, gdist_sets* s, int64_t r0, int64_t r1, int64_t 
 void group_reduce(gdist_ctx* ctx, WalkSource& src, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int ntypes,
                   const int32_t* rlabels, const int32_t* clabels, gdist_group_side* out, int64_t* bad);
 
+// width_sweep.hip — the sketch error at every size of a list (gdist_width_sweep)
+// every argument checked by the caller, nsets >= 2, nsizes >= 1; method: SORTED or
+// BITSET (resolved by the caller). sizes: host. rows: size and dwarves are the
+// caller's, every other field and *pairs written here
+void width_sweep(gdist_ctx* ctx, gdist_sets* sets, const gdist_sets* sk, int nsizes, const int32_t* sizes,
+                 int method, unsigned flags, gdist_width_row* rows, int64_t* pairs);
+
 // within.hip — every pair within max_dist as CSR (gdist_within)
 // method: SORTED or BITSET (resolved by the caller); ignored for sketches.
 // rowptr: r1 - r0 + 1 entries, written whole; col_out / d_out: the first

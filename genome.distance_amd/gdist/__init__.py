@@ -8,10 +8,10 @@ from . import _lib
 from ._lib import (AMBIG_DEFAULT, AMBIG_KEEP, AMBIG_SKIP, BITSET_KEEP_SINGLETONS, CLOSEST_KEEP_SELF, CLOSEST_MAX_N,
                    EMPTY_NAN, GROUP_MAX_TYPES, HIST_MAX_EDGES, METHOD_AUTO,
                    METHOD_BITSET, METHOD_SORTED, NO_CASE_FOLD, QUERY_ALL, QUERY_ANY_LE, QUERY_ARGMIN,
-                   SKETCH_JACCARD, STRAND_BOTH, STRAND_CANON, STRAND_FWD, UPPER_TRIANGLE, GdistError)
+                   SKETCH_JACCARD, STRAND_BOTH, STRAND_CANON, STRAND_FWD, UPPER_TRIANGLE, WIDTH_MAX_SIZES, GdistError)
 from .fasta import Sequence, read_fasta, write_fasta
 from .javafmt import java_double, java_doubles
-from .kmers import (Context, DeviceBuffer, GroupStats, Histogram, HostBuffer, release_device_cache, KmerSets, KmerType, LSHIndex, SequenceKmers, SketchSets, option_names,
+from .kmers import (Context, DeviceBuffer, GroupStats, Histogram, HostBuffer, release_device_cache, KmerSets, KmerType, LSHIndex, SequenceKmers, SketchSets, WidthSweep, option_names,
                     options_from_env, triangle_partition)
 
 __version__ = _lib.lib.gdist_version().decode()

@@ -26,6 +26,7 @@ QUERY_ALL, QUERY_ANY_LE, QUERY_ARGMIN = 0, 1, 2
 CLOSEST_KEEP_SELF, CLOSEST_MAX_N = 0x1000, 512
 GROUP_MAX_TYPES = 8
 HIST_MAX_EDGES = 1023
+WIDTH_MAX_SIZES = 512
 UNIQUE_ID_BYTES = 128
 OPTION_DEFAULT = -(1 << 63)   # GDIST_OPTION_DEFAULT
 
@@ -35,6 +36,12 @@ class GroupSide(C.Structure):
     _fields_ = [("n", C.c_int64), ("ones", C.c_int64), ("nans", C.c_int64),
                 ("min", C.c_double), ("max", C.c_double), ("mean", C.c_double), ("sdev", C.c_double),
                 ("sum", C.c_uint64 * 2), ("sumsq", C.c_uint64 * 3)]
+
+
+class WidthRow(C.Structure):
+    """gdist_width_row: the sketch error at one sketch size (gdist_width_sweep)."""
+    _fields_ = [("size", C.c_int32), ("pad", C.c_int32), ("dwarves", C.c_int64), ("differing", C.c_int64),
+                ("max_err", C.c_double), ("total", C.c_double), ("mean", C.c_double), ("sum", C.c_uint64 * 2)]
 
 
 class GdistError(RuntimeError):
@@ -154,6 +161,7 @@ _SIGS = {
     "gdist_group_stats": (C.c_int, [_ctxp, _setp, _i64, _i64, _i64, _i64, C.c_int, _u32, C.c_int, _i32p, _vp, _i64p]),
     "gdist_group_stats_merge": (C.c_int, [_vp, _i64p, _vp, _i64p, C.c_int]),
     "gdist_ctx_group_stats_timing": (C.c_int, [_ctxp, _dblp, _dblp]),
+    "gdist_width_sweep": (C.c_int, [_ctxp, _setp, _setp, C.c_int, _i32p, C.c_int, _u32, _vp, _i64p]),
     "gdist_within": (C.c_int, [_ctxp, _setp, _i64, _i64, _i64, _i64, C.c_int, _u32, _dbl, _i64, _i64p, _i64p, _dblp,
                                _i64p]),
     "gdist_ctx_within_timing": (C.c_int, [_ctxp, _dblp, _dblp]),

@@ -401,6 +401,36 @@ class GroupStats:
         return self.mean + self.sdev
 
 
+class WidthSweep:
+    """Result of width_sweep (gdist_width_sweep): the error of the sketch
+    distance against the exact one at each of S sketch sizes.
+
+    pairs: the pairs i < j with exact distance < 1.0. Per size k: size int32
+    [S]; dwarves int64 [S] (signatures shorter than the size); differing int64
+    [S] (pairs whose two distances differ); max_err, total, mean float64 [S]
+    (the largest relative error, their sum, total / pairs; 0.0 without
+    pairs); sum: [S] Python ints, the exact sum of rint(e * 2^62). `rows` is
+    the C array (gdist_width_row [S])."""
+
+    def __init__(self, rows, pairs: int):
+        self.rows, self.pairs = rows, int(pairs)
+
+        def arr(name, dtype):
+            return np.array([getattr(r, name) for r in rows], dtype=dtype)
+        self.size = arr("size", np.int32)
+        self.dwarves, self.differing = arr("dwarves", np.int64), arr("differing", np.int64)
+        self.max_err, self.total, self.mean = (arr("max_err", np.float64), arr("total", np.float64),
+                                               arr("mean", np.float64))
+        self.sum = [int(r.sum[0]) | (int(r.sum[1]) << 64) for r in rows]
+
+    def __len__(self) -> int:
+        return len(self.rows)
+
+    def tobytes(self) -> bytes:
+        """The struct array and the pair count as the library wrote them."""
+        return bytes(self.rows) + self.pairs.to_bytes(8, "little", signed=True)
+
+
 class Histogram:
     """Result of histogram (gdist_histogram): how the distances of a region are
     distributed over E ascending bucket edges.
@@ -1188,6 +1218,25 @@ class KmerSets(_Handle):
         h = C.c_void_p()
         L.check(L.lib.gdist_sketch_build(self.ctx.h, self.h, int(width), C.byref(h)))
         return SketchSets(self.ctx, h)
+
+    def width_sweep(self, sk: "SketchSets", sizes, method: int = L.METHOD_AUTO, flags: int = 0) -> WidthSweep:
+        """The error of the sketch distance at every sketch size of `sizes`
+        (strictly increasing, at most WIDTH_MAX_SIZES) in one walk of the
+        pairs (gdist_width_sweep; WidthProcessor.java:153-208). `sk` is
+        self.sketches(W) for a W >= sizes[-1]: its signatures' prefixes are
+        the sketches of every smaller size. flags: 0 or SKETCH_JACCARD. Every
+        field is exact, so the result depends on neither method nor block
+        sizes; neither distance table leaves the device."""
+        sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int64).reshape(-1))
+        if sz.size and (sz.min() < -2**31 or sz.max() >= 2**31):
+            raise ValueError("a sketch size does not fit 32 bits")
+        sz = sz.astype(np.int32)
+        rows = (L.WidthRow * len(sz))()
+        pairs = C.c_int64(0)
+        L.check(L.lib.gdist_width_sweep(self.ctx.h, self.h, sk.h, len(sz), L.ptr(sz, C.c_int32) if len(sz) else None,
+                                        int(method), int(flags), C.addressof(rows) if len(sz) else None,
+                                        C.byref(pairs)))
+        return WidthSweep(rows, pairs.value)
 
     def __getitem__(self, i: int) -> "SequenceKmers":
         n = len(self)

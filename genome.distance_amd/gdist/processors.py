@@ -313,13 +313,22 @@ def sketch_sizes(min_size: int, max_size: int, step: int) -> list[int]:
 
 
 def width_process_group(group_id: str, sets: KmerSets, sizes: Sequence[int], out: TextIO,
-                        target_error: float = 0.001) -> int | None:
+                        target_error: float = 0.001, sweep: bool = False) -> int | None:
     """WidthProcessor.ProcessGroup (WidthProcessor.java:153-208): exact
     all-pairs on the device, then per sketch size the sketch all-pairs and the
     relative error |r - s| * 2 / (r + s) over every pair i < j whose distances
     differ, summed in the reference's i-major order; one output line per size.
     Returns the smallest size whose mean error meets the target
-    (INVALID_TARGET_SIZE if none), or None for a group with no pair < 1.0."""
+    (INVALID_TARGET_SIZE if none), or None for a group with no pair < 1.0.
+
+    sweep: one sets.sketches(max(sizes)) and one KmerSets.width_sweep
+    (gdist_width_sweep) answer every size, with neither table leaving the
+    device. The lines are the same; the total is then the exact sum of the
+    errors quantised to 2^-62 instead of the i-major fp64 sum, so a printed
+    mean can differ only where it lies within ~1e-10 of a rounding boundary
+    of its fourth decimal."""
+    if sweep and len(sizes):
+        return _width_sweep_group(group_id, sets, sizes, out, target_error)
     n = len(sets)
     _, D = sets.matrix(upper=True)
     iu = np.triu_indices(n, 1)                      # (i, j) in i-major order
@@ -349,14 +358,41 @@ def width_process_group(group_id: str, sets: KmerSets, sizes: Sequence[int], out
     return min_good
 
 
+def _width_sweep_group(group_id: str, sets: KmerSets, sizes: Sequence[int], out: TextIO,
+                       target_error: float) -> int | None:
+    """width_process_group over one width_sweep call: the same lines and the
+    same min_good logic."""
+    sizes = list(sizes)
+    sk = sets.sketches(max(sizes))
+    try:
+        # a call takes at most WIDTH_MAX_SIZES sizes: a longer list goes in parts
+        parts = [sets.width_sweep(sk, sizes[c:c + L.WIDTH_MAX_SIZES])
+                 for c in range(0, len(sizes), L.WIDTH_MAX_SIZES)]
+    finally:
+        sk.free()
+    pairs = parts[0].pairs
+    if pairs == 0:
+        return None
+    min_good = INVALID_TARGET_SIZE
+    for res in parts:
+        for k in range(len(res)):
+            size, mean, max_err = int(res.size[k]), float(res.mean[k]), float(res.max_err[k])
+            out.write(f"{group_id}\t{size:8d}\t{pairs:8d}\t{int(res.dwarves[k]):8d}\t{java_format_f(mean, 8, 4)}\t"
+                      f"{java_format_f(max_err, 8, 4)}\n")
+            if size < min_good and mean <= target_error:
+                min_good = size
+    return min_good
+
+
 def width_processor(rows: Iterable[tuple[str, str]], min_size: int, max_size: int, out: TextIO,
                     step: int = 10, max_group: int = 1000, target_error: float = 0.001, kmer_size: int = 8,
-                    ctx: Context | None = None) -> int:
+                    ctx: Context | None = None, sweep: bool = False) -> int:
     """WidthProcessor (width): `rows` are (group id, protein sequence) in input
     order; consecutive rows of one group form a group, split at max_group
     (WidthProcessor.java:117-131). Validation as validateParms
     (WidthProcessor.java:88-106). Returns the target sketch size (the largest
-    per-group minimum, INVALID_TARGET_SIZE when some group had none)."""
+    per-group minimum, INVALID_TARGET_SIZE when some group had none). sweep:
+    every group through one width_sweep call (width_process_group)."""
     if min_size > max_size:
         raise ParseFailureException("Minimum sketch size cannot be larger than maximum.")
     if step <= 0:
@@ -372,7 +408,7 @@ def width_processor(rows: Iterable[tuple[str, str]], min_size: int, max_size: in
     def flush(gid, prots):
         nonlocal target
         sets = KmerSets.from_sequences(prots, kmer_size, KmerType.PROT, 0, ctx)
-        good = width_process_group(gid, sets, sizes, out, target_error)
+        good = width_process_group(gid, sets, sizes, out, target_error, sweep)
         if good is not None and good > target:
             target = good
 

@@ -30,6 +30,8 @@
  *                          over chosen pairs                     WidthProcessor.java:183-192
  *   gdist_sketch_greedy_reps the distReps / fastaReps selection with
  *                          Sketch.distance as the distance       DistanceRepsProcessor.java:185-200,227-237
+ *   gdist_width_sweep      the per-size loop of ProcessGroup: sketch
+ *                          error at every sketch size of a list  WidthProcessor.java:153-208
  *   gdist_closest          getClosest(kmers, n, maxDist), exhaustively
  *                          (every column, no LSH buckets)        MashProcessor.java:150, FindProcessor.java:110
  *                          --maxDist of the genomes table        GenomeProcessor.java:58-60,89
@@ -584,6 +586,56 @@ int  gdist_group_stats_merge(gdist_group_side* acc, int64_t* bad_acc, const gdis
  * call made with option "time_kernels" = 1: the matrix kernels and the reduce
  * kernel apart; -1 when the call was not timed. */
 int  gdist_ctx_group_stats_timing(gdist_ctx* ctx, double* matrix_ms, double* reduce_ms);
+
+/* ---- sketch error at every sketch size --------------------------------- */
+/* The per-size loop of WidthProcessor.ProcessGroup (WidthProcessor.java:
+ * 153-208) as one walk of the pairs, with neither table leaving the device.
+ * `sets` is the group's kmer collection and `sk` a GDIST_SKETCH collection
+ * of the same context and the same number of sets, set i the bottom-W
+ * signature of set i: what gdist_sketch_build(ctx, sets, W, ...) returns for
+ * a W >= sizes[nsizes - 1]. The first s hashes of a bottom-W signature are
+ * the bottom-s signature, so sk holds the sketches of every listed size.
+ * Both collections are only read (a method may build its index on `sets`,
+ * as in gdist_closest).
+ *
+ * For every pair i < j: r is the exact distance (the bit pattern
+ * gdist_intersect_matrix writes; method AUTO / SORTED / BITSET resolved as
+ * gdist_closest resolves it) and, per size s = sizes[k], s_k the sketch
+ * distance gdist_sketch_matrix would write for the two size-s sketches under
+ * the same flags (0, or GDIST_SKETCH_JACCARD). *pairs counts the pairs with
+ * r < 1.0 (WidthProcessor.java:162). Row k describes size s over the pairs
+ * with r != s_k (pairs with r == 1.0 included, WidthProcessor.java:186-192):
+ * differing their number, max_err the largest e = |r - s_k| * 2.0 / (r + s_k)
+ * (fp64, no contraction; 0.0 when none differ), sum the exact integer sum of
+ * E = rint(e * 2^62) (ties to even; e <= 2, so E <= 2^63), total = sum *
+ * 2^-62 (one rounding to nearest even, then an exact scale) and mean = total
+ * / pairs. dwarves counts the sets whose signature in sk is shorter than s
+ * (WidthProcessor.java:180). Every field is an integer result or comes from
+ * one by a fixed expression, so the rows depend on neither the block sizes
+ * (options "closest_rows" / "closest_cols": the walk is gdist_closest's),
+ * the method nor the run. The reference adds the doubles e in i-major
+ * order; `total` is the sum of the errors quantised to 2^-62 and may differ
+ * from that sum in its last digits.
+ *
+ * nsets < 2 or nsizes == 0: GDIST_OK, *pairs = 0, every row's size and
+ * dwarves set and its other fields zero. EINVAL, decided before any work
+ * (the outputs stay untouched): a null handle, null pairs, null sizes or
+ * rows_out with nsizes > 0, sets of another context, `sets` a sketch
+ * collection or `sk` not one, differing set counts, nsizes outside
+ * 0..GDIST_WIDTH_MAX_SIZES, sizes not strictly increasing or < 1, a last
+ * size above the width of sk, any flag but GDIST_SKETCH_JACCARD
+ * (GDIST_EMPTY_NAN too: a NaN has no place in an integer sum), an unknown
+ * method, SORTED on a bitsets-only collection. */
+#define GDIST_WIDTH_MAX_SIZES 512
+typedef struct {
+    int32_t  size, pad;              /* sizes[k]; 0 */
+    int64_t  dwarves, differing;     /* signatures shorter than size; pairs with r != s_k */
+    double   max_err, total, mean;   /* mean: total / pairs; 0.0 when pairs == 0 */
+    uint64_t sum[2];                 /* sum of rint(e * 2^62), little-endian limbs */
+} gdist_width_row;
+int  gdist_width_sweep(gdist_ctx* ctx, const gdist_sets* sets, const gdist_sets* sk,
+                       int nsizes, const int32_t* sizes /* host */, int method, unsigned flags,
+                       gdist_width_row* rows_out /* [nsizes] */, int64_t* pairs);
 
 /* ---- every pair within a distance -------------------------------------- */
 /* The documented maxDist filter of the genomes table (GenomeProcessor.java:35,
